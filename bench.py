@@ -15,7 +15,18 @@ frame-parallel, ONE all-gather of the flow fields, kernels / robustness / merge 
 star's): frames one per rank, ONE reduce-scatter of the float32 accumulators.  The output stays sharded by rows
 (`--gather` adds the gather to rank 0).  Total work is fixed, so scaling is "strong".
 
-Rank 0 prints ONE JSON line: metric "output Mpix/s" (scale^2 * H * W / time per burst), plus
+Rank 0 prints ONE JSON line: metric "output Mpix/s" (scale^2 * H * W / time per burst).  A plain run sets up, runs --warmup
+steps, times EXACTLY --steps steps in one block (`ms_per_step` = that block's time / --steps) and prints the line; nothing
+else is measured.  --dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned (the output
+image [sH, sW, 3], float32) as DIR/output.npy when it fits in 64 MB with its mask, else as DIR/output_sample.npy (a fixed
+sample: sorted distinct flat indices drawn by torch's CPU generator with seed 0) and DIR/output_crop.npy (the
+full-resolution centre crop of 1024 x 1024 pixels).  Every file holds finite numbers: a NaN of the output (0 / 0 where a
+border pixel's window holds no sample of a colour, as in the reference) is written as 0 and flagged with 1 in the
+matching *_nonfinite.npy.  The burst is seeded: the same arguments give the same inputs run after run.
+
+--full adds everything else the benchmark measures or checks (the legs below, each guarded; --no-h2d, --no-c5 and
+--no-cpu-baseline leave single legs out): --reps blocks of --steps steps (default 5) behind an untimed settle block, the
+headline being the MEDIAN block, and the shader clock measured in one more block; N > 1 both strategies; and
   value_incl_h2d  the same with the frames starting in HOST memory (the reference's timer spans its uploads:
                   super_resolution.py:103-195): page-locked float32 arrays (with pcie_floor_ms / pcie_floor_frac),
                   h2d.*_u16: uint16 sensor counts normalised on the device (half the PCIe bytes), h2d.value_numpy_pageable:
@@ -96,17 +107,64 @@ def parse_args():
                     help="N > 1, rows: bound on |flow_y| in pixels for the sub-image halo (no host read in the step); "
                          "default: measured from the gathered flows (one scalar read per burst)")
     ap.add_argument("--cpu-cores", type=int, default=None, help="worker processes of the CPU baseline (default: all cores)")
-    ap.add_argument("--reps", type=int, default=5, help="repetitions of the timed block of --steps steps: ms_per_step is "
-                                                        "the MEDIAN block, ms_per_step_min / _max the spread")
+    ap.add_argument("--reps", type=int, default=None, help="repetitions of the timed block of --steps steps: ms_per_step is "
+                                                           "the MEDIAN block, ms_per_step_min / _max the spread (default: "
+                                                           "5 with --full, else 1)")
+    ap.add_argument("--full", action="store_true", help="also run every other leg: repeated blocks + shader clock, eager "
+                    "launch timing and rooflines, host-resident, weight_fp64, denoiser, C5, CPU baseline + parity; N > 1: "
+                    "both strategies")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's output to DIR/*.npy "
+                    "(float32, at most 64 MB: a fixed sample + centre crop of a larger image; NaN / inf written as 0 and "
+                    "flagged in *_nonfinite.npy)")
     ap.add_argument("--no-c5", action="store_true", help="skip the optional 48 MP x 20 x3 (C5 geometry) leg")
     ap.add_argument("--denoiser", action="store_true", help="the main workload with the accumulated-robustness merge denoiser on "
-                    "(kernel traces of that path; the default run times it as the ms_per_step_denoiser leg)")
+                    "(kernel traces of that path; --full times it as the ms_per_step_denoiser leg)")
     ap.add_argument("--weight-fp64", action="store_true", help="the main workload with config.hip.weight_fp64 (the reference's "
                                                                "float64 weight chain on every pixel; kernel traces)")
     args = ap.parse_args()
     if args.engine is not None and args.backend != "gloo":
         ap.error("--engine (a foreign per-rank engine: launch-plumbing tests) is only accepted with --backend gloo")
+    if args.reps is None:
+        args.reps = 5 if args.full else 1
     return args
+
+
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+DUMP_CROP = 1024       # edge of the centre crop written next to the sample of a larger output
+
+
+def dump_outputs(out, directory):
+    """Write one output tensor under `directory` as .npy files of finite numbers: NAME.npy holds the values (float32;
+    float64 stays float64) with every NaN / inf replaced by 0, NAME_nonfinite.npy (float32) is 1 exactly there.  (The
+    reference algorithm's output is 0 / 0 = NaN where a border pixel's window holds no sample of a colour.)  The whole
+    tensor when values + mask fit in DUMP_BYTES, else half the budget for a fixed sample of values and half for a
+    full-resolution centre crop of at most DUMP_CROP x DUMP_CROP pixels."""
+    import math
+
+    import numpy as np
+    import torch
+
+    os.makedirs(directory, exist_ok=True)
+    if out.dtype != torch.float64:
+        out = out.float()
+    per_value = out.element_size() + 4  # value + float32 mask
+
+    def save(name, t):
+        bad = ~torch.isfinite(t)
+        np.save(os.path.join(directory, name + ".npy"), torch.where(bad, torch.zeros_like(t), t).cpu().numpy())
+        np.save(os.path.join(directory, name + "_nonfinite.npy"), bad.float().cpu().numpy())
+        return [name + ".npy", name + "_nonfinite.npy"]
+
+    if out.numel() * per_value <= DUMP_BYTES:
+        return save("output", out)
+    gen = torch.Generator().manual_seed(0)
+    k = DUMP_BYTES // 2 // per_value
+    idx = torch.unique(torch.randint(0, out.numel(), (k,), generator=gen), sorted=True)
+    names = save("output_sample", out.reshape(-1)[idx.to(out.device)])
+    px = out[0, 0].numel()  # values per pixel
+    c = min(DUMP_CROP, out.shape[0], out.shape[1], math.isqrt(DUMP_BYTES // 2 // (px * per_value)))
+    y0, x0 = (out.shape[0] - c) // 2, (out.shape[1] - c) // 2
+    return names + save("output_crop", out[y0:y0 + c, x0:x0 + c])
 
 
 def respawn_under_torchrun(args):
@@ -206,7 +264,8 @@ def main():
     timed_call.on = False
     timed_call.sink = ev
     timed_call.steps = 0
-    hmerge._lib.call = timed_call
+    if args.full:  # (a plain run launches through the library's own call)
+        hmerge._lib.call = timed_call
 
     # shader clock DURING a timed block: a one-wave probe (hhsr_clock_probe) sleeps on a side stream next to the block's
     # kernels for ~60 % of its expected duration and reports shader cycles per 100 MHz tick
@@ -292,8 +351,11 @@ def main():
 
     def step(r=ref, c=comp):
         timed_call.steps += int(timed_call.on)
-        return hdist.main_sharded(r, c, cfg, engine=engine, gather=args.gather, strategy=args.strategy,
-                                  max_flow=args.max_flow)[0]
+        step.last = hdist.main_sharded(r, c, cfg, engine=engine, gather=args.gather, strategy=args.strategy,
+                                       max_flow=args.max_flow)[0]
+        return step.last
+
+    step.last = None  # (what the last step returned: --dump-outputs)
 
     def barrier():
         if world > 1:
@@ -322,11 +384,16 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
-    timed_call.on = True
+    timed_call.on = args.full
     # EXACTLY --steps steps per timed block, --reps blocks back to back: the headline is the median block
     ms_blocks, sclk = timed_reps(step, args.steps, args.reps, 0)
     timed_call.on = False
     timed_region_s = time.perf_counter() - t_region
+    if args.dump_outputs and rank == 0 and step.last is not None:
+        names = dump_outputs(step.last, args.dump_outputs)
+        print(f"bench.py: last timed step's output -> {', '.join(os.path.join(args.dump_outputs, n) for n in names)}",
+              file=sys.stderr)
+    step.last = None
     sp = spread(ms_blocks)
     ms_per_step = sp["median"]
     out_pix = round(scale * H) * round(scale * W)
@@ -372,7 +439,7 @@ def main():
         dist.all_reduce(g_any, op=dist.ReduceOp.MAX)
         graphed = bool(int(g_any.item()))
     ms_eager, ev_steps = None, timed_call.steps  # (not graphed: every step of the timed blocks launched the kernel itself)
-    if graphed:
+    if graphed and args.full:
         # the timed steps were graph replays: no Python launch to bracket with events.  The dominant kernel's launch
         # duration comes from a few eager steps of the same workload right after (same kernel, same inputs)
         import copy
@@ -400,7 +467,7 @@ def main():
     # this rank count next to it — so a SCALE value can be checked against (compute per rank) + (RCCL time).  Optional leg:
     # guarded on every rank, and a watchdog prints the line and ends the process if a collective of this leg hangs.
     strategies, emulated = None, None
-    if world > 1:
+    if world > 1 and args.full:
         import threading
 
         def give_up():
@@ -567,7 +634,7 @@ def main():
 
     # ---- H2D-inclusive legs: the reference's scope (frames are host arrays when the timer starts); N = 1 only --------
     h2d = None
-    if on_gpu and not args.no_h2d and world == 1:
+    if args.full and on_gpu and not args.no_h2d and world == 1:
         import copy
 
         steps_h = max(3, args.steps // 2)
@@ -649,7 +716,7 @@ def main():
     # (merge.py:319-426); the timed step above computes them in float32 within the stated tolerance.
     # config.hip.weight_fp64 runs the float64 chain on every pixel (the generic per-pixel kernel): what reference-typed
     # arithmetic costs on this chip.  N = 1, guarded like the other legs.
-    if on_gpu and world == 1 and not args.no_h2d:
+    if args.full and on_gpu and world == 1 and not args.no_h2d:
         import copy
 
         try:
@@ -666,7 +733,7 @@ def main():
     # ---- the accumulated-robustness merge denoiser on (merge.py:223-228; off in configs/default.yaml): the comp frames through
     # the same fused merge, the float64 robustness sum in one pass (hhsr_rob_sum), then merge_ref with its overwrite / widen
     # rules + divide.  N = 1, guarded.
-    if on_gpu and world == 1 and not args.no_h2d:
+    if args.full and on_gpu and world == 1 and not args.no_h2d:
         import copy
 
         try:
@@ -683,7 +750,7 @@ def main():
 
     # ---- the C5 geometry on ONE GPU (48 MP x 20 frames x3 -> 432 MP; BASELINE.json configs[4] is this workload over 8 GPUs):
     # the x3 merge kernel's numbers in the driver's own record.  Optional, guarded, N = 1, headline run only.
-    if on_gpu and world == 1 and headline and not args.no_c5 and not args.no_h2d:
+    if args.full and on_gpu and world == 1 and headline and not args.no_c5 and not args.no_h2d:
         import copy
 
         try:
@@ -739,7 +806,7 @@ def main():
 
     # ---- CPU baseline (all host cores) + parity with attribution, on a crop of the same burst ----------------------
     cpu, parity = None, None
-    if rank == 0 and world == 1 and on_gpu and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and on_gpu and not args.no_cpu_baseline:
         try:
             import oracle
 

@@ -477,7 +477,7 @@ def test_bench_launches_ranks_itself():
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--engine",
                         os.path.abspath(__file__) + ":OracleEngine", "--height", "512", "--width", "512", "--frames", "3",
-                        "--steps", "1", "--warmup", "0", "--no-cpu-baseline"], capture_output=True, text=True, env=env,
+                        "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline"], capture_output=True, text=True, env=env,
                        timeout=550)
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert p.returncode == 0 and len(lines) == 1, p.stderr[-2000:]
@@ -487,3 +487,40 @@ def test_bench_launches_ranks_itself():
     # both strategies in the one record (the driver passes --gpus N only), the launcher's and the group's rank counts agree
     assert rec["ranks_agree"] and set(rec["strategies"]) == {"rows", "reduce"} and not rec.get("errors")
     assert rec["strategies"]["rows"]["headline"] and rec["strategies"]["reduce"]["value"] > 0
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run times exactly --steps steps in one block and runs no other leg; --dump-outputs writes the
+    last timed step's output, the same array run after run (seeded burst).  NumPy test double as the engine."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(steps, warmup, out_dir):
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--backend", "gloo", "--engine",
+                            os.path.abspath(__file__) + ":OracleEngine", "--height", "512", "--width", "512", "--frames", "3",
+                            "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(out_dir)],
+                           capture_output=True, text=True, timeout=280)
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert p.returncode == 0 and len(lines) == 1, p.stderr[-2000:]
+        return json.loads(lines[0])
+
+    a = run(2, 0, tmp_path / "a")
+    b = run(1, 1, tmp_path / "b")
+    for rec, steps in ((a, 2), (b, 1)):
+        assert rec["steps"] == steps and rec["reps"] == 1 and rec["ms_per_step_blocks"] == [rec["ms_per_step"]]
+        assert rec["ms_per_step"] > 0 and rec["value"] > 0 and rec["unit"] == "Mpix/s" and rec["higher_is_better"]
+        assert rec["dtype"] == "f32" and rec["settle_steps"] == 0 and not rec.get("errors")
+        assert rec["roofline"] is None and rec["cpu_baseline"] is None and rec["ms_per_step_eager"] is None
+    for d in ("a", "b"):
+        assert sorted(os.listdir(tmp_path / d)) == ["output.npy", "output_nonfinite.npy"]
+    out_a, out_b = np.load(tmp_path / "a" / "output.npy"), np.load(tmp_path / "b" / "output.npy")
+    bad_a, bad_b = np.load(tmp_path / "a" / "output_nonfinite.npy"), np.load(tmp_path / "b" / "output_nonfinite.npy")
+    assert out_a.shape == bad_a.shape == (1024, 1024, 3) and out_a.dtype == bad_a.dtype == np.float32
+    assert np.isfinite(out_a).all() and set(np.unique(bad_a)) <= {0.0, 1.0}  # NaN of the output: 0 + flag
+    assert (out_a[bad_a == 1] == 0).all() and bad_a.mean() < 0.01
+    np.testing.assert_array_equal(out_a, out_b)
+    np.testing.assert_array_equal(bad_a, bad_b)

@@ -2432,7 +2432,7 @@ def _bench_shared_gpu(ranks, *extra):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(ranks), "--backend", "gloo", *extra,
-                        "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=850)  # (host legs: N = 1 only)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=850)  # (host legs: N = 1 only)
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert p.returncode == 0 and len(lines) == 1, p.stderr[-3000:]
     return json.loads(lines[0])

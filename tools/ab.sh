@@ -55,7 +55,7 @@ done
 for ((i = 1; i <= BENCH; i++)); do
   for cfg in "$@"; do
     E=$(envof "$cfg"); LABEL="${cfg%%[@,]*}"
-    env $E python "$ROOT/bench.py" --no-cpu-baseline --no-h2d --steps 15 --warmup 4 $GEOM 2>/dev/null | python -c "
+    env $E python "$ROOT/bench.py" --full --no-cpu-baseline --no-h2d --steps 15 --warmup 4 $GEOM 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); r = d.get('roofline') or {}
 print('$LABEL step', d['ms_per_step'], 'eager', d['ms_per_step_eager'], r.get('kernel'), r.get('avg_launch_ms'))"

@@ -18,9 +18,9 @@ bash tools/pmc_merge.sh "k_merge_xs" $NAME/pmc_x3 --no-h2d --steps 1 --warmup 0 
 python tools/pmc_report.py $OUT/pmc_x3 k_merge_xs profiles/${NAME}_pmc_merge_x3.json $CS/hhsr_merge.h,$CS/hhsr_merge_xs.hip "6000x8000x20 x3" \
   "tools/pmc_merge.sh k_merge_xs (bench.py --no-cpu-baseline --no-h2d --steps 1 --warmup 0 --height 6000 --width 8000 --scale 3), profiles/${NAME}_pmc_merge_x3.md" > $OUT/pmc_x3.md
 cp profiles/${NAME}_pmc_merge_x3.json $OUT/pmc_merge_x3.json
-T0=$(date +%s); python bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err; echo "bench.py default run: $(( $(date +%s) - T0 )) s wall" > $OUT/bench_n1.time
-python bench.py --height 6000 --width 8000 --scale 3 --frames 20 --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_c5.json 2> /dev/null
-python bench.py --frames 8 --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_c2.json 2> /dev/null
+T0=$(date +%s); python bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err; echo "bench.py --full run: $(( $(date +%s) - T0 )) s wall" > $OUT/bench_n1.time
+python bench.py --full --height 6000 --width 8000 --scale 3 --frames 20 --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_c5.json 2> /dev/null
+python bench.py --full --frames 8 --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_c2.json 2> /dev/null
 bash tools/kernel_trace.sh $NAME/kt 5 > /dev/null 2>&1
 bash tools/pmc_all.sh $NAME/pmc_all > /dev/null 2>&1
 # host-resident legs, the copy / kernel timelines of one host-resident step, measured bounds

@@ -20,9 +20,9 @@ if has pmc_x3; then
   cp profiles/${NAME}_pmc_merge_x3.json $OUT/pmc_merge_x3.json
 fi
 if has bench; then
-  T0=$(date +%s); python bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err; echo "bench.py default run: $(( $(date +%s) - T0 )) s wall" > $OUT/bench_n1.time
-  python bench.py --height 6000 --width 8000 --scale 3 --frames 20 --steps 5 --warmup 2 --no-cpu-baseline --no-h2d > $OUT/bench_c5.json 2> /dev/null
-  python bench.py --frames 8 --steps 10 --warmup 3 --no-cpu-baseline --no-h2d > $OUT/bench_c2.json 2> /dev/null
+  T0=$(date +%s); python bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err; echo "bench.py --full run: $(( $(date +%s) - T0 )) s wall" > $OUT/bench_n1.time
+  python bench.py --full --height 6000 --width 8000 --scale 3 --frames 20 --steps 5 --warmup 2 --no-cpu-baseline --no-h2d > $OUT/bench_c5.json 2> /dev/null
+  python bench.py --full --frames 8 --steps 10 --warmup 3 --no-cpu-baseline --no-h2d > $OUT/bench_c2.json 2> /dev/null
 fi
 if has traces; then
   bash tools/kernel_trace.sh $NAME/kt 5 > /dev/null 2>&1

@@ -13,7 +13,7 @@ if [ "${1:-all}" != ranks ]; then
 for i in 1 2 3; do
   for v in r4 fork; do
     setv $v
-    python bench.py --no-cpu-baseline --no-h2d --steps 20 --warmup 5 2>/dev/null | python -c "
+    python bench.py --full --no-cpu-baseline --no-h2d --steps 20 --warmup 5 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); print('$v: step', d['ms_per_step'], 'eager', d['ms_per_step_eager'])"
   done

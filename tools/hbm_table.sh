@@ -4,7 +4,7 @@ set -u
 cd /tmp && export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/hbm
 rm -rf $OUT && mkdir -p $OUT
-ARGS="--no-cpu-baseline --no-c5 --streams 1 --steps 1 --warmup 1"
+ARGS="--full --no-cpu-baseline --no-c5 --streams 1 --steps 1 --warmup 1"
 for C in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $C --kernel-include-regex "k_" --output-format csv -d $OUT/$C -o p -- python $GRAFT_REPO_ROOT/bench.py --reps 1 $ARGS > $OUT/$C.log 2>&1
 done

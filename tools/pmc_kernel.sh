@@ -4,6 +4,7 @@
 set -u
 cd /tmp && export TMPDIR=/tmp
 RX="$1"; NAME="$2"; shift 2
+set -- --full "$@"  # (every leg of the benchmark, not only its timed steps)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$NAME
 mkdir -p $OUT
 i=0
