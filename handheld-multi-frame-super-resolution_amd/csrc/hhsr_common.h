@@ -114,4 +114,3 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? l
 
 // Python/Numba `max(0, z)`: returns z only when z > 0, so NaN -> 0 (reference quirk D10).
 __device__ __forceinline__ double pymax0(double z) { return z > 0.0 ? z : 0.0; }
-__device__ __forceinline__ float pymax0f(float z) { return z > 0.0f ? z : 0.0f; }

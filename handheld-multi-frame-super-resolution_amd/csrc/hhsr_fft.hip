@@ -327,7 +327,7 @@ __global__ void __launch_bounds__(NT, fft_rows_wpe(NT)) k_rows_fwd(FftFrames fr,
     float2* tw = fl;
     float2* buf = tw + ((twlen + 1) & ~1);  // 16-byte aligned
     batched_for<float2, NT>(twlen, tid, [&](int k) { return twM[k]; }, [&](int k, float2 v) { tw[k] = v; });
-    // persistent workgroups: the grid is one resident round (HHSR_FFT_PERSIST), every workgroup walks the row blocks
+    // persistent workgroups: the grid is one resident round (hhsr_fft_lowpass: `persist`), every workgroup walks the row blocks
     // (row_block): one twiddle copy and one dispatch per workgroup slot instead of per block
     const int nb = (H + RB - 1) / RB;
     for (int it = 0, vblk; (vblk = row_block<RB>(it, nb * fr.n)) >= 0; ++it) {
@@ -549,7 +549,7 @@ static std::vector<float2> pass_twiddles(const HhsrRadices& rad);
 
 // Radix schedule: fewest passes over the supported radices, then the smallest maximum radix (registers, idle
 // lanes), then an odd / small first radix (the Ns = 1 pass stores with stride R: even R collide on LDS banks).
-// HHSR_FFT_RADIX_MAX (experiments) caps the radix; 5 reproduces the original 5/4/3/2 schedule.
+// factorize caps the radix at 16.
 static const int k_radices[] = {16, 15, 14, 12, 10, 9, 8, 7, 6, 5, 4, 3, 2};
 
 static void radix_search(int n, int rmax, int cap, int nt, int depth, int* cur, int& best_n, int* best, int& best_max) {
@@ -575,8 +575,7 @@ static void radix_search(int n, int rmax, int cap, int nt, int depth, int* cur, 
 
 // nb: sequences transformed together by one workgroup of nt threads (every pass runs nb * n / R butterflies)
 static bool factorize(int n, int nb, HhsrRadices& out, int nt = FFT_NT) {
-    const char* e = getenv("HHSR_FFT_RADIX_MAX");
-    const int rmax = e ? atoi(e) : 16;  // (radix 20 / 25 butterflies would exceed the 128-VGPR budget)
+    const int rmax = 16;  // (radix 20 / 25 butterflies would exceed the 128-VGPR budget)
     int cur[HHSR_MAX_RADICES], best[HHSR_MAX_RADICES], best_n = HHSR_MAX_RADICES + 1, best_max = 1 << 30;
     radix_search(n, rmax, nb * n, nt, 0, cur, best_n, best, best_max);
     if (best_n > HHSR_MAX_RADICES) return false;
@@ -586,8 +585,7 @@ static bool factorize(int n, int nb, HhsrRadices& out, int nt = FFT_NT) {
     for (int i = 1; i < best_n; ++i)
         if (collide(best[i]) < collide(best[first]) || (collide(best[i]) == collide(best[first]) && best[i] > best[first]))
             first = i;
-    static const int pow_min = getenv("HHSR_FFT_POW_MIN") ? atoi(getenv("HHSR_FFT_POW_MIN")) : HHSR_FFT_POW_MIN;
-    out.pow_min = pow_min;
+    out.pow_min = HHSR_FFT_POW_MIN;
     out.n = 0;
     out.r[out.n++] = best[first];
     for (int i = 0; i < best_n; ++i)
@@ -646,11 +644,9 @@ static std::vector<float2> pass_twiddles(const HhsrRadices& rad) {
 // First choice: one row per 256-thread workgroup when its passes fit 256 threads and row + twiddles fit 32 KB (five
 // workgroups per CU; see FFT_NT_SMALL) — rows up to 4000 pixels.  HHSR_FFT_NT_ROWS=512 (experiments / tests) skips it.
 static int pick_rb(int M, HhsrRadices& rad, int& nt) {
-    const char* e = getenv("HHSR_FFT_RB");  // experiments
-    const int forced = e ? atoi(e) : 0;
     const char* ent = getenv("HHSR_FFT_NT_ROWS");
     const int forced_nt = ent ? atoi(ent) : 0;
-    if ((!forced || forced == 1) && forced_nt != FFT_NT && factorize(M, 1, rad, FFT_NT_SMALL) &&
+    if (forced_nt != FFT_NT && factorize(M, 1, rad, FFT_NT_SMALL) &&
         sizeof(float2) * (((pass_twiddles(rad).size() + 1) & ~(size_t)1) + (size_t)M) <= 32 * 1024) {
         nt = FFT_NT_SMALL;
         return 1;
@@ -659,7 +655,6 @@ static int pick_rb(int M, HhsrRadices& rad, int& nt) {
     const int cands[3] = {2, 4, 1};
     for (int c = 0; c < 3; ++c) {
         const int rb = cands[c];
-        if (forced && rb != forced) continue;
         if (rb * (M / 2) >= 65536) continue;
         if (!factorize(M, rb, rad)) continue;
         if (sizeof(float2) * (pass_twiddles(rad).size() + (size_t)rb * M) > 76 * 1024 && rb > 1) continue;
@@ -749,9 +744,8 @@ void hhsr_fft_destroy(HhsrFft& f) {
 int hhsr_fft_lowpass(const HhsrFft& f, const float* const* srcs, float* const* dsts, int n, hipStream_t s) {
     // row kernels: at most one resident round of workgroups (3 per CU by their 48 kB of LDS, 5 per CU for the 256-thread
     // single-row workgroups with 32 kB), each walking several blocks
-    static const int persist_env = getenv("HHSR_FFT_PERSIST") ? atoi(getenv("HHSR_FFT_PERSIST")) : -1;
     const bool small = f.nt_rows == FFT_NT_SMALL;
-    const int persist = persist_env >= 0 ? persist_env : small ? 1280 : 768;
+    const int persist = small ? 1280 : 768;
     // unnormalised inverse transforms multiply by (W/2) and H
     const float norm = (float)(1.0 / ((double)(f.W / 2) * (double)f.H));
     // Frames per round: the kept spectra of a round's frames live between the three kernels, and they should live in the
@@ -761,8 +755,6 @@ int hhsr_fft_lowpass(const HhsrFft& f, const float* const* srcs, float* const* d
     const size_t spectrum = sizeof(float2) * f.tstride, budget = (size_t)112 << 20;
     int per = (int)(budget / (spectrum ? spectrum : 1));
     per = per < 1 ? 1 : per > f.batch ? f.batch : per;
-    static const int per_env = getenv("HHSR_FFT_ROUND") ? atoi(getenv("HHSR_FFT_ROUND")) : 0;  // (experiments)
-    if (per_env > 0) per = per_env > f.batch ? f.batch : per_env;
     for (int n0 = 0; n0 < n; n0 += per) {  // (the plan holds f.batch spectra)
         FftFrames fr;
         fr.n = n - n0 < per ? n - n0 : per;

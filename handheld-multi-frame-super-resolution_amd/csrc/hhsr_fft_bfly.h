@@ -1,5 +1,4 @@
-// Register butterflies of the in-LDS FFTs (hhsr_fft.hip; also included by the wave-synchronous experiment kept under
-// tools/experiments/fft_wave/).
+// Register butterflies of the in-LDS FFTs (hhsr_fft.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

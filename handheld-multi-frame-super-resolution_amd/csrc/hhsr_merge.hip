@@ -352,14 +352,10 @@ static int merge_burst_impl(const float* const* raws, const float* const* flows,
     const bool p2 = scale_is_pow2(scale);
     // kernel choice.  LDS-staged tile kernel: integer scale, 16-px HR workgroups inside one flow tile, windows fit the
     // LDS arrays; x2 kernels: one thread per LR pixel (4 HR pixels), 32 x 32 HR workgroups inside one flow tile.
-    // kflags HHSR_MERGE_FORCE_* (validation / A-B measurements) restrict the choice; the environment variables
-    // HHSR_MERGE_NO_LDS / _NO_QUAD / _X2_V1 do the same for a whole process and are read once.
-    static const int env_force = (getenv("HHSR_MERGE_NO_LDS") ? HHSR_MERGE_FORCE_GENERIC : 0) |
-                                 (getenv("HHSR_MERGE_NO_QUAD") ? HHSR_MERGE_FORCE_TILE : 0) |
-                                 (getenv("HHSR_MERGE_X2_V1") ? HHSR_MERGE_FORCE_X2V1 : 0);
+    // kflags HHSR_MERGE_FORCE_* (validation references) restrict the choice.
     // monochrome sensors: the x2 tile kernel with a per-pixel covariance window (k_merge_burst_quad<.., MONO>); every other
     // scale takes the generic kernel (the tile / wave-per-class kernels are laid out for the Bayer covariance grid)
-    const int force = kflags | env_force;
+    const int force = kflags;
     const int iscale = (int)scale;
     const bool tiled = !f64 && (double)iscale == scale && iscale >= 1 && ((int64_t)ts * iscale) % MT == 0 &&
                        n_frames > 0 && row0 % MT == 0 && !(force & HHSR_MERGE_FORCE_GENERIC) && !(mono && iscale != 2);
@@ -411,8 +407,7 @@ static int merge_burst_impl(const float* const* raws, const float* const* flows,
     }
     if (!f64 && !(flags & HHSR_MERGE_STORE_CLASSES)) {  // the border bands the float32 kernels skipped, with the reference's float64 weight chain
         const int nf = n_frames + ((flags & HHSR_MERGE_DO_REF) ? 1 : 0);
-        static const bool border_v1 = getenv("HHSR_MERGE_BORDER_V1") != nullptr;  // A/B switch, read once
-        if (nf >= 2 && nf <= 64 && !border_v1) {  // lane = (pixel, frame)
+        if (nf >= 2 && nf <= 64) {  // lane = (pixel, frame)
             const int ppw = 64 / nf;
             const int64_t npx = (int64_t)(g.bt + g.bb) * g.sW + (int64_t)(g.bl + g.br) * (g.sH - g.bt - g.bb);
             const int64_t nwaves = (npx + ppw - 1) / ppw;

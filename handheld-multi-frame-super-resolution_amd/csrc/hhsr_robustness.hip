@@ -8,7 +8,6 @@
 // Arithmetic follows the reference's Numba typing: float64 weights and noise-model
 // maths, float32 storage and float32 running sums that are rounded after every tap.
 #include "hhsr_common.h"
-#include <stdlib.h>
 
 // (the guide image + local statistics pass lives in hhsr_kernels.hip: it shares its raw tile with the kernel
 // covariances, k_frame_stats)
@@ -18,13 +17,6 @@ __device__ __forceinline__ double dodgson(double x) {  // utils_image.py:399-406
     if (a <= 0.5) return -2.0 * a * a + 1.0;
     if (a <= 1.5) return a * a - 5.0 / 2.0 * a + 1.5;
     return 0.0;
-}
-
-__device__ __forceinline__ float dodgsonf(float x) {
-    const float a = fabsf(x);
-    if (a <= 0.5f) return fmaf(-2.0f * a, a, 1.0f);
-    if (a <= 1.5f) return fmaf(a, a, fmaf(-2.5f, a, 1.5f));
-    return 0.0f;
 }
 
 // Interpolates the NC channels of a [NC][lh][lw] map at raw pixel (y, x) displaced by (fx, fy).
@@ -846,9 +838,8 @@ extern "C" int hhsr_rob_frame(const float* comp_means, int lh, int lw, const flo
     HHSR_ARG(lh > 0 && lw > 0 && ts > 0 && ncurve > 0);
     const int H = 2 * lh, W = 2 * lw;
     HHSR_ARG(ny * ts >= H && nx * ts >= W);
-    static const bool no_row4 = getenv("HHSR_ROB_NO_ROW4") != nullptr;  // read once
     const bool vec4 = W % 4 == 0 && (((uintptr_t)ref_means | (uintptr_t)ref_sigma_sq | (uintptr_t)ref_curve_index |
-                                      (uintptr_t)R) & 15) == 0 && !no_row4;
+                                      (uintptr_t)R) & 15) == 0;
     if (ts % RF_T == 0 && ref_curve_index && ncurve <= 1024 && vec4)
         hipLaunchKernelGGL(k_rob_frame_row4, dim3(hhsr_cdiv(W, RF_BX), hhsr_cdiv(H, RF_BY)), dim3(256), 0,
                            (hipStream_t)stream, comp_means, lh, lw, ref_means, ref_sigma_sq, ref_curve_index,
@@ -874,10 +865,9 @@ extern "C" int hhsr_rob_frames(const float* const* comp_means, int n_frames, int
     HHSR_ARG(ref_means && ref_sigma_sq && diff_curve && lh > 0 && lw > 0 && ts > 0 && ncurve > 0);
     const int H = 2 * lh, W = 2 * lw;
     HHSR_ARG(ny * ts >= H && nx * ts >= W);
-    static const bool no_group = getenv("HHSR_ROB_NO_GROUP") != nullptr;  // A/B switch, read once
     bool vec4 = W % 4 == 0 && (((uintptr_t)ref_means | (uintptr_t)ref_sigma_sq | (uintptr_t)ref_curve_index) & 15) == 0;
     for (int n = 0; n < n_frames; ++n) vec4 = vec4 && ((uintptr_t)R[n] & 15) == 0;
-    if (no_group || !(ts % RF_T == 0 && ref_curve_index && ncurve <= 1024 && vec4)) {
+    if (!(ts % RF_T == 0 && ref_curve_index && ncurve <= 1024 && vec4)) {
         if (!S) {
             hhsr_set_error("hhsr_rob_frames: S = NULL (weights evaluated inside the kernel) needs the grouped kernel: "
                            "ts %% 16 == 0, W %% 4 == 0, packed curve indices, 16-byte aligned planes");

@@ -50,7 +50,6 @@ The engine that does the per-rank compute is injected so that the sharding / exc
 a GPU (tests run it on gloo with the NumPy oracle as the engine, world_size 2 and 3).
 """
 import math
-import os
 
 import torch
 import torch.distributed as dist
@@ -642,7 +641,7 @@ class RowsPlan:
             ny_nx = _flow_grid_of(ref.shape, cfg)
             eng.pipe, eng.device = pipe, dev
             first = stage_frames(stages[0], n, G, rank) if stages else []
-            fuse_ref = bool(first) and os.environ.get("HHSR_ROWS_SPLIT_REF") is None  # (A/B switch, read at capture)
+            fuse_ref = bool(first)
             self.g_ref_a = None
             if not fuse_ref:
                 self.g_ref_a = torch.cuda.CUDAGraph()

@@ -40,7 +40,7 @@ def shared_streams(device):
         pool = _stream_pool.setdefault(idx, [])
         while len(pool) < DEFAULT_STREAMS:
             pool.append(torch.cuda.Stream(dev))
-        hit = _shared[idx] = (main, torch.cuda.Stream(dev, priority=-1), torch.cuda.Stream(dev, priority=-1))
+        hit = _shared[idx] = (main, torch.cuda.Stream(dev, priority=-1))
     return hit
 
 
@@ -167,6 +167,16 @@ class HostBurstRunner:
     asynchronously on the current stream as usual and belongs to the runner: valid until its next call."""
 
     COPY_THREADS = 12  # (the MI355X boxes of this project give a container 16 CPUs' worth of quota: more threads get throttled)
+    # A chunk's copies are queued when the previous chunk's are done, not all 20 up front: with many copies pending on
+    # the stream the copy engine sometimes settles at HALF rate (1.6 instead of 0.85 ms per 48 MB for whole bursts,
+    # rocprofv3 --memory-copy-trace; seen after compute-only phases of the process, tools/debug/host_leg_timing.py with
+    # HHSR_PRELUDE) — queued a chunk at a time it stays at full rate in every state measured, at the price of a gap
+    # per chunk (17.3 -> 17.7 ms for 960 MB; 17.3 again with UPLOAD_AHEAD below).
+    # UPLOAD_AHEAD: chunks whose copies are queued AHEAD of the chunk the host is waiting for (page-locked frames): with 0
+    # the copy engine idles from a chunk's last copy until the host has woken up, launched the chunk's graph and queued the
+    # next copies (~130 us per chunk, 19.3 -> 19.1 ms per float32 burst); 1 and 2 measure the same, "all" is the half-rate
+    # mode above
+    UPLOAD_AHEAD = 1
 
     def __init__(self, config, device):
         self.config, self.device = config, device
@@ -179,23 +189,10 @@ class HostBurstRunner:
         # stream mapped to the same queue starts after the LAST copy (tools/debug/hwqueue_probe.py: 7 of 8 compute streams
         # blocked for 8.7 ms; with the upload stream in the high-priority queue set: none).  Both streams are shared by
         # all runners of the process (shared_streams).
-        self.main, self.up, self.up2 = shared_streams(device)
-        import os
+        self.main, self.up = shared_streams(device)
         import threading
 
         self._lock = threading.Lock()  # one burst at a time per runner (static staging, shared streams)
-
-        self.two_up = os.environ.get("HHSR_TWO_UPLOAD_STREAMS") == "1"  # (experiment: copies alternate between two streams)
-        # A chunk's copies are queued when the previous chunk's are done, not all 20 up front: with many copies pending on
-        # the stream the copy engine sometimes settles at HALF rate (1.6 instead of 0.85 ms per 48 MB for whole bursts,
-        # rocprofv3 --memory-copy-trace; seen after compute-only phases of the process, tools/debug/host_leg_timing.py with
-        # HHSR_PRELUDE) — queued a chunk at a time it stays at full rate in every state measured, at the price of a gap
-        # per chunk (17.3 -> 17.7 ms for 960 MB; 17.3 again with upload_ahead below).  HHSR_PACED_UPLOADS=0: everything up front.
-        self.paced_uploads = os.environ.get("HHSR_PACED_UPLOADS", "1") != "0"
-        # chunks whose copies are queued AHEAD of the chunk the host is waiting for (paced uploads): with 0 the copy engine
-        # idles from a chunk's last copy until the host has woken up, launched the chunk's graph and queued the next copies
-        # (~130 us per chunk, 19.3 -> 19.1 ms per float32 burst); 1 and 2 measure the same, "all" is the half-rate mode above
-        self.upload_ahead = int(os.environ.get("HHSR_UPLOAD_AHEAD", "1"))
 
     def _eager(self, ref_img, comp_imgs):
         from .super_resolution import main
@@ -309,7 +306,7 @@ class HostBurstRunner:
         with torch.cuda.device(dev):
             st.stage = torch.empty((n + 1, H, W), dtype=frames[0].dtype, device=dev)
             st.pin = None
-            st.main, st.up, st.up2 = self.main, self.up, self.up2
+            st.main, st.up = self.main, self.up
             for i, f in enumerate(frames):  # valid content for the capture-time launches' validation paths
                 st.stage[i].copy_(f)
             torch.cuda.synchronize(dev)
@@ -415,7 +412,6 @@ class HostBurstRunner:
 
         dev = self.device
         cur = torch.cuda.current_stream(dev)
-        n = len(frames) - 1
         pinned = all(f.is_pinned() for f in frames)
         futs = None
         if not pinned:
@@ -440,8 +436,6 @@ class HostBurstRunner:
                 futs.append([st.pool.submit(np.copyto, st.pin_np[i, a:b], src[a:b]) for a, b in zip(cuts[:-1], cuts[1:]) if b > a])
         with torch.cuda.device(dev):
             st.up.wait_stream(st.main)   # the previous burst's kernels are done with the device staging buffers
-            if self.two_up:
-                st.up2.wait_stream(st.main)
             st.main.wait_stream(cur)
             consumed = getattr(self, "_consumed", None)
             if consumed is not None:  # the previous call's clone of the static result (call_cloned), on whatever stream
@@ -454,16 +448,11 @@ class HostBurstRunner:
                     for f in futs[i]:
                         f.result()
                     src = st.pin[i]
-                up = st.up2 if (self.two_up and i % 2) else st.up
-                with torch.cuda.stream(up):
+                with torch.cuda.stream(st.up):
                     st.stage[i].copy_(src, non_blocking=True)
-                    st.e_up[i].record(up)
+                    st.e_up[i].record(st.up)
 
             upload(0)
-            paced = futs is not None or self.paced_uploads
-            if not paced:  # (page-locked frames, HHSR_PACED_UPLOADS=0: all copies queued up front, back to back)
-                for i in range(1, n + 1):
-                    upload(i)
             # The graphs are launched HOST-PACED: the host waits for a chunk's last copy, then launches its graph.  Queued
             # up front behind event waits they did not start before the LAST copy had finished (measured: first kernel at
             # 9.0 ms of a 9.0 ms upload sequence) — HIP streams share a few hardware queues, and a barrier packet that
@@ -475,12 +464,11 @@ class HostBurstRunner:
                 st.e_ref.record(st.main)
             queued = 0  # chunks whose copies are queued
             for c, (idx, s, g) in enumerate(zip(st.chunks, st.streams, st.g_chunks)):
-                while paced and queued < len(st.chunks) and queued <= c + (self.upload_ahead if futs is None else 0):
+                while queued < len(st.chunks) and queued <= c + (self.UPLOAD_AHEAD if futs is None else 0):
                     for i in st.chunks[queued]:
                         upload(1 + i)
                     queued += 1
-                for i in (idx if self.two_up else idx[-1:]):
-                    st.e_up[1 + i].synchronize()  # (one upload stream: copies complete in order)
+                st.e_up[1 + idx[-1]].synchronize()  # (one upload stream: copies complete in order)
                 with torch.cuda.stream(s):
                     s.wait_event(st.e_ref)
                     g.replay()

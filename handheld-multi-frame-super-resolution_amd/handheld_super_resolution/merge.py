@@ -1,5 +1,4 @@
 """Alg. 4 / Alg. 11 accumulation (reference merge.py) plus the fused burst merge."""
-import os
 
 import torch
 
@@ -10,10 +9,6 @@ from . import _lib
 KERNEL_ISO, WEIGHT_F64, FORCE_GENERIC, FORCE_TILE, FORCE_X2V1, SENSOR_MONO = 1, 2, 4, 8, 16, 32
 REF_DIVIDE, REF_FAST = 64, 128  # hhsr_accumulate_ref only (include/hhsr.h HHSR_REF_DIVIDE, HHSR_REF_FAST)
 _FORCE = {"auto": 0, "generic": FORCE_GENERIC, "tile": FORCE_TILE, "x2_v1": FORCE_X2V1}
-# process-wide A/B switches, read once like the library reads them
-_ENV_FORCE = ((FORCE_GENERIC if os.environ.get("HHSR_MERGE_NO_LDS") else 0) |
-              (FORCE_TILE if os.environ.get("HHSR_MERGE_NO_QUAD") else 0) |
-              (FORCE_X2V1 if os.environ.get("HHSR_MERGE_X2_V1") else 0))
 
 
 def _common(config):
@@ -25,7 +20,7 @@ def _common(config):
     f64 = bool(hip.get("weight_fp64", False)) if hip is not None else False
     force = _FORCE[str(hip.get("merge_kernel", "auto"))] if hip is not None else 0
     return float(config.scale), ((KERNEL_ISO if config.merging.kernel == "iso" else 0) | (WEIGHT_F64 if f64 else 0) |
-                                 force | _ENV_FORCE | (SENSOR_MONO if config.mode != "bayer" else 0))
+                                 force | (SENSOR_MONO if config.mode != "bayer" else 0))
 
 
 def merge(comp_img, alignments, covs, r, num, den, cfa_pattern, config):

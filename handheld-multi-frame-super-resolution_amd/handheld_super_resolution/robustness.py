@@ -5,11 +5,6 @@ import torch
 from . import _lib
 
 
-import os as _os
-
-_NO_GROUP = bool(_os.environ.get("HHSR_ROB_NO_GROUP"))  # the library's A/B switch, read once like the library reads it
-
-
 def _wb3(white_balance):
     wb = [float(v) for v in (white_balance.tolist() if hasattr(white_balance, "tolist") else white_balance)]
     if len(wb) < 3:
@@ -302,8 +297,7 @@ def compute_robustness_group(comp_imgs, ref_local_means, flows, noise_model, con
     sigma_sq, curve_index = ref_sigma_sq
     # the grouped kernel evaluates the per-tile flow-irregularity weight S itself (one launch less per frame); the
     # per-frame fall-back kernels of hhsr_rob_frames need the S maps — same test as in the library
-    inline_s = (int(ts) % 16 == 0 and W % 4 == 0 and curve_index is not None and diff_curve.numel() <= 1024
-                and not _NO_GROUP)
+    inline_s = int(ts) % 16 == 0 and W % 4 == 0 and curve_index is not None and diff_curve.numel() <= 1024
     for f in flows:
         _check_flow_view(f, flow_rows)
     S = None if inline_s else [compute_s(f, t.Mt, t.s1, t.s2, flow_rows) for f in flows]

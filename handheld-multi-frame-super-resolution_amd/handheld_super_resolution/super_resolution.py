@@ -86,7 +86,8 @@ class _Staged:
 _upload_streams = {}  # device index -> the stream all prefetched uploads are queued on, in frame order
 
 
-_LATE_FORK = os.environ.get("HHSR_LATE_FORK") is not None  # A/B switch (read once): side streams fork behind the reference precompute
+_LATE_FORK = os.environ.get("HHSR_LATE_FORK") is not None  # (read once) side streams fork behind the reference precompute:
+# the way out of the early-fork ordering contract (BurstPipeline._on_streams)
 
 
 class BurstPipeline:

@@ -312,3 +312,26 @@ def test_robustness_sum_keeps_float64_decisions():
         assert torch.equal(a64 <= mfc, s64 <= mfc) and torch.equal(a64 < mfc, s64 < mfc), mfc
         far = (s64 - float(mfc)).abs() > 4 * float(np.spacing(m32))  # away from the threshold the map IS the rounded sum
         assert torch.equal(a[far], s64.to(torch.float32)[far])
+
+
+def test_environment_reads_are_the_allowlisted_ones():
+    """Every HHSR_* environment variable that the library or the package reads.  A/B switches whose losing side was
+    measured are not kept: a process that inherits one would silently run a path that no test runs."""
+    import glob
+    import os
+    import re
+
+    pkg = os.path.dirname(hsr.__file__)
+    csrc = os.path.join(os.path.dirname(pkg), "csrc")
+    files = (glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")) +
+             glob.glob(os.path.join(pkg, "*.py")))
+    assert len(files) > 20
+    read = re.compile(r"""(?:getenv\(|environ\.get\(|environ\[)\s*["'](HHSR_[A-Z0-9_]*)["']""")
+    names = set()
+    for f in files:
+        with open(f, encoding="utf-8") as fh:
+            names.update(read.findall(fh.read()))
+    assert names == {"HHSR_FFT_NC", "HHSR_FFT_NT_ROWS", "HHSR_FFT_STATIC",  # tests: FFT paths their sizes do not reach
+                     "HHSR_GREY_PLAN",                                       # tests: the library's FFT plans
+                     "HHSR_LIB",                                             # another build of the library (tools/ab.sh)
+                     "HHSR_LATE_FORK"}                                       # out of the early-fork ordering contract

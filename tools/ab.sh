@@ -4,7 +4,7 @@
 # environment switches of the library.  Run on an MI355X (gpurun), from the repo root.
 #
 #   tools/ab.sh [options] CONFIG [CONFIG ...]
-#     CONFIG   label[@variant][,ENV=VALUE ...]     "default" = the committed library; e.g.  pf5@pf5  nt256@nt256,HHSR_FFT_PERSIST=1280
+#     CONFIG   label[@variant][,ENV=VALUE ...]     "default" = the committed library; e.g.  pf5@pf5  nt256@nt256,HHSR_FFT_STATIC=0
 #   options
 #     --kernels REGEX     rocprofv3 --kernel-trace of an eager one-stream bench run per config; prints the per-kernel rows
 #                         matching REGEX (plus the total)
@@ -13,8 +13,8 @@
 #     --size "H W F S"    burst geometry for --kernels / --bench (default: the headline 3000 4000 20 2; C5: "6000 8000 20 3")
 #     --steps N           steps of the traced run (default 5)
 # Examples (what round 4 ran as tools/debug/r04_call*.sh):
-#   tools/ab.sh --kernels "k_rows|k_cols" --tests "grey or fft" default pf@pf,HHSR_FFT_PERSIST=512      (FFT prefetch variants)
-#   tools/ab.sh --bench 3 default serial,HHSR_MERGE_BORDER_SERIAL=1                                     (border bands)
+#   tools/ab.sh --kernels "k_rows|k_cols" --tests "grey or fft" default pf@pf,HHSR_FFT_STATIC=0        (FFT prefetch variants)
+#   tools/ab.sh --bench 3 default serial@serial                                                       (border bands)
 #   tools/ab.sh --bench 2 --size "6000 8000 20 3" default nw2@nw2                                       (x3 merge variants)
 set -u
 ROOT=${GRAFT_REPO_ROOT:-$PWD}

@@ -34,10 +34,9 @@ bash tools/debug/kt_c5.sh 2>&1 | grep -v amdgpu.ids > $OUT/kernel_trace_c5.md
 python tools/debug/emulate_ranks.py --worlds 1,2,4,8 --steps 10 2>&1 | grep "^{" > $OUT/emulate_ranks_c3.jsonl
 python tools/debug/emulate_ranks.py --worlds 2,4,8 --steps 10 --strategies rows --stage-frames 4 2>&1 | grep "^{" > $OUT/emulate_ranks_c3_staged.jsonl
 python tools/debug/emulate_ranks.py --worlds 1,2,4,8 --steps 3 --height 6000 --width 8000 --scale 3 --strategies rows 2>&1 | grep "^{" > $OUT/emulate_ranks_c5.jsonl
-# round 5: the overlap changes of the per-rank step A/B; the headline burst and the C5 geometry against the oracle at full size
+# the headline burst and the C5 geometry against the oracle at full size
 # (two-sided; minutes of all host cores).  (The micro-benchmarks and probes of round 4 — VALU rates, occupancy, LDS patterns,
 # counter calibration, hardware queues, border cost, covariance-inline bound — did not change: profiles/r04_*.)
-bash tools/debug/ab_rows_overlap.sh > $OUT/rows_overlap_ab.txt 2>&1
 python tools/full_size_oracle.py --workers 8 --out $OUT/c3_full_oracle.txt > /dev/null 2>&1
 python tools/full_size_oracle.py --height 3000 --width 8000 --frames 5 --scale 3 --workers 4 --out $OUT/c5_geometry_oracle.txt > /dev/null 2>&1
 find $OUT -name "*agent_info*" -delete
