@@ -60,6 +60,55 @@ def acc_pattern(oh, ow, phase):
     return (((i * 7 + j * 13 + c * 3 + phase) % 17) / 17.0 + 0.25).astype(np.float32)
 
 
+def smooth(rng, h, w, sigma=2.0):
+    """A smooth random field in [0, 1] (float32 [h, w])."""
+    from scipy.ndimage import gaussian_filter
+
+    f = gaussian_filter(rng.standard_normal((h + 16, w + 16)), sigma)[8:8 + h, 8:8 + w]
+    return ((f - f.min()) / (f.max() - f.min())).astype(np.float32)
+
+
+def bm_inputs(rng, ts, r, ny, nx, shift):
+    """(reference level [ny ts, nx ts], moving level 3 rows / 5 columns smaller and shifted by `shift`, incoming flow
+    [ny, nx, 2] with half-integer ties and a few tiles whose search windows leave the moving level)."""
+    h, w = ny * ts, nx * ts
+    big = smooth(rng, h + 32, w + 32, 1.5)
+    ref = big[16:16 + h, 16:16 + w].copy()
+    sy, sx = shift
+    mov = big[16 + sy:16 + sy + h - 3, 16 + sx:16 + sx + w - 5].copy()
+    mov += 0.01 * rng.standard_normal(mov.shape).astype(np.float32)
+    flow = rng.uniform(-1.6, 1.6, (ny, nx, 2)).astype(np.float32)
+    flow[0, 0] = (0.5, -0.5)
+    flow[0, 1] = (1.5, 2.5)
+    flow[1, 0] = (-1.5, -2.5)
+    flow[-1, -1] = (6.0, 5.0)
+    flow[0, -1] = (-7.0, -6.0)
+    return ref, mov, flow
+
+
+def check_bm(got, want, cost, what, atol=0.0, max_ties=1):
+    """Integer block-matching result: equal to the oracle's, except on tiles whose two best costs are tied within 1e-4
+    relative (the kernel sums float32 FMAs per lane in a fixed order, the oracle float64) — at most `max_ties` of them."""
+    diff = np.abs(got - want).max(-1) > atol
+    for ty, tx in zip(*np.nonzero(diff)):
+        c = np.sort(cost[ty, tx].ravel())
+        assert (c[1] - c[0]) <= 1e-4 * max(1.0, abs(c[0])), (what, ty, tx, c[:3], got[ty, tx], want[ty, tx])
+    assert diff.sum() <= max_ties, (what, int(diff.sum()))
+
+
+def merge_frames(H, W, n, ts, seed, cfg):
+    """(ref, [(comp, flow, covs, r)] * n): merge inputs with random flows in [-2, 2] and robustness in [0, 1]."""
+    ref, comp, _ = synth.make_burst(H, W, n + 1, seed=seed, max_shift=1.5)
+    rng = np.random.default_rng(seed)
+    fr = []
+    for k in range(n):
+        flow = rng.uniform(-2, 2, ((H + ts - 1) // ts, (W + ts - 1) // ts, 2)).astype(np.float32)
+        r = rng.random((H, W), dtype=np.float32)
+        covs = oracle.estimate_kernels(comp[k], cfg)
+        fr.append((comp[k], flow, covs, r))
+    return ref, fr
+
+
 def assert_close(a, b, rtol, atol, what="", max_bad_frac=0.0):
     """allclose with NaN == NaN and inf == inf; optionally tolerate a fraction of outliers."""
     a = np.asarray(a, dtype=np.float64)

@@ -9,7 +9,8 @@ import pytest
 import torch
 
 import oracle
-from helpers import flipped_tiles, assert_explained, base_config, acc_pattern, assert_close
+from helpers import (flipped_tiles, assert_explained, base_config, acc_pattern, assert_close, smooth, bm_inputs, check_bm,
+                     merge_frames)
 
 pytestmark = pytest.mark.gpu
 
@@ -38,13 +39,6 @@ def T(a, dtype=torch.float32):
 
 def N(t):
     return t.detach().cpu().numpy()
-
-
-def smooth(rng, h, w, sigma=2.0):
-    from scipy.ndimage import gaussian_filter
-
-    f = gaussian_filter(rng.standard_normal((h + 16, w + 16)), sigma)[8:8 + h, 8:8 + w]
-    return ((f - f.min()) / (f.max() - f.min())).astype(np.float32)
 
 
 # ------------------------------------------------------------------------------------------ grey / pyramid
@@ -191,43 +185,17 @@ def test_grad_hessian(ts):
     assert_close(N(H), oH, 2e-5, 1e-7, "H")
 
 
-def _bm_inputs(rng, ts, r, ny, nx, shift):
-    h, w = ny * ts, nx * ts
-    big = smooth(rng, h + 32, w + 32, 1.5)
-    ref = big[16:16 + h, 16:16 + w].copy()
-    sy, sx = shift
-    mov = big[16 + sy:16 + sy + h - 3, 16 + sx:16 + sx + w - 5].copy()
-    mov += 0.01 * rng.standard_normal(mov.shape).astype(np.float32)
-    flow = rng.uniform(-1.6, 1.6, (ny, nx, 2)).astype(np.float32)
-    flow[0, 0] = (0.5, -0.5)
-    flow[0, 1] = (1.5, 2.5)
-    flow[1, 0] = (-1.5, -2.5)
-    flow[-1, -1] = (6.0, 5.0)
-    flow[0, -1] = (-7.0, -6.0)
-    return ref, mov, flow
-
-
-def _check_bm(got, want, cost, what, atol=0.0, max_ties=1):
-    """Integer block-matching result: equal to the oracle's, except on tiles whose two best costs are tied within 1e-4
-    relative (the kernel sums float32 FMAs per lane in a fixed order, the oracle float64) — at most `max_ties` of them."""
-    diff = np.abs(got - want).max(-1) > atol
-    for ty, tx in zip(*np.nonzero(diff)):
-        c = np.sort(cost[ty, tx].ravel())
-        assert (c[1] - c[0]) <= 1e-4 * max(1.0, abs(c[0])), (what, ty, tx, c[:3], got[ty, tx], want[ty, tx])
-    assert diff.sum() <= max_ties, (what, int(diff.sum()))
-
-
 @pytest.mark.parametrize("ts,r", [(8, 4), (16, 4), (16, 1), (32, 4), (64, 4), (16, 9)])
 def test_bm_l2(ts, r):
     rng = np.random.default_rng(4 + ts + r)
-    ref, mov, flow = _bm_inputs(rng, ts, r, 5, 6, (2, -3))
+    ref, mov, flow = bm_inputs(rng, ts, r, 5, 6, (2, -3))
     cfg = base_config(ts=16)
     cfg.block_matching.tuning.tile_sizes = [ts] * 4
     cfg.block_matching.tuning.search_radii = [r] * 4
     f = T(flow)
     block_matching.align_lvl_block_matching_L2(T(ref), None, T(mov), f, 0, cfg)
     want, cost = oracle.bm_l2(ref, mov, flow, ts, r, return_cost=True)
-    _check_bm(N(f), want, cost, f"bm_l2 ts={ts} r={r}")
+    check_bm(N(f), want, cost, f"bm_l2 ts={ts} r={r}")
 
 
 def test_bm_l2_accepts_the_reference_tiled_tensor():
@@ -235,7 +203,7 @@ def test_bm_l2_accepts_the_reference_tiled_tensor():
     alignment.py:56-60, 131): same result as with the level itself; a mismatching tensor raises TypeError."""
     ts, r = 16, 4
     rng = np.random.default_rng(3)
-    ref, mov, flow = _bm_inputs(rng, ts, r, 5, 6, (2, -3))
+    ref, mov, flow = bm_inputs(rng, ts, r, 5, 6, (2, -3))
     cfg = base_config(ts=16)
     cfg.block_matching.tuning.tile_sizes = [ts] * 4
     cfg.block_matching.tuning.search_radii = [r] * 4
@@ -261,20 +229,20 @@ def test_bm_l2_golden(golden):
         f = T(g[tag + "_flow_in"])
         block_matching.align_lvl_block_matching_L2(T(g[tag + "_ref"]), None, T(g[tag + "_mov"]), f, 0, cfg)
         _, cost = oracle.bm_l2(g[tag + "_ref"], g[tag + "_mov"], g[tag + "_flow_in"], ts, r, return_cost=True)
-        _check_bm(N(f), g[tag + "_flow_out"], cost, "golden " + tag)
+        check_bm(N(f), g[tag + "_flow_out"], cost, "golden " + tag)
 
 
 @pytest.mark.parametrize("ts,r", [(16, 1), (16, 4), (32, 2), (64, 1)])
 def test_bm_l1(ts, r):
     rng = np.random.default_rng(40 + ts + r)
-    ref, mov, flow = _bm_inputs(rng, ts, r, 4, 5, (1, -1))
+    ref, mov, flow = bm_inputs(rng, ts, r, 4, 5, (1, -1))
     cfg = base_config(ts=16)
     cfg.block_matching.tuning.tile_sizes = [ts] * 4
     cfg.block_matching.tuning.search_radii = [r] * 4
     f = T(flow)
     block_matching.align_lvl_block_matching_L1(T(ref), T(mov), f, 0, cfg)
     want, cost = oracle.bm_l1(ref, mov, flow, ts, r, return_cost=True)
-    _check_bm(N(f), want, cost, f"bm_l1 ts={ts} r={r}")
+    check_bm(N(f), want, cost, f"bm_l1 ts={ts} r={r}")
     f = T(flow)
     block_matching.align_lvl_block_matching_L1(T(ref), T(mov), f, 0, cfg, effective=True)
     assert_close(N(f), oracle.bm_l1(ref, mov, flow, ts, r, effective=True), 0, 0, "L1 effective")
@@ -329,7 +297,7 @@ def test_fused_align_level(ts, r, metric):
     """hhsr_align_level == hhsr_bm_* followed by hhsr_ica (and == the oracle), incl. border tiles."""
     rng = np.random.default_rng(100 + ts + r)
     ny, nx = 5, 6
-    ref, mov, flow = _bm_inputs(rng, ts, r, ny, nx, (1, -2))
+    ref, mov, flow = bm_inputs(rng, ts, r, ny, nx, (1, -2))
     cfg = base_config(ts=16, metrics=(metric,) * 4)
     cfg.block_matching.tuning.tile_sizes = [ts] * 4
     cfg.block_matching.tuning.search_radii = [r] * 4
@@ -347,7 +315,7 @@ def test_fused_align_level(ts, r, metric):
         assert_close(N(f_fused), want, 0, 2e-4, f"fused vs oracle ts={ts} {metric}")
     else:
         _, cost = (oracle.bm_l2 if metric == "L2" else oracle.bm_l1)(ref, mov, flow, ts, r, return_cost=True)
-        _check_bm(N(f_fused), want, cost, f"fused vs oracle ts={ts} {metric}", atol=2e-4)
+        check_bm(N(f_fused), want, cost, f"fused vs oracle ts={ts} {metric}", atol=2e-4)
 
 
 @pytest.mark.parametrize("mode", ["nearest", "bilinear", "bicubic"])
@@ -602,18 +570,6 @@ def test_merge_ref_denoiser_golden(golden):
         assert_close(N(d3), g[tag + "denref"], 2e-5, 1e-6, "fast denref")
 
 
-def _frames(H, W, n, ts, seed, cfg):
-    ref, comp, _ = synth.make_burst(H, W, n + 1, seed=seed, max_shift=1.5)
-    rng = np.random.default_rng(seed)
-    fr = []
-    for k in range(n):
-        flow = rng.uniform(-2, 2, ((H + ts - 1) // ts, (W + ts - 1) // ts, 2)).astype(np.float32)
-        r = rng.random((H, W), dtype=np.float32)
-        covs = oracle.estimate_kernels(comp[k], cfg)
-        fr.append((comp[k], flow, covs, r))
-    return ref, fr
-
-
 @pytest.mark.parametrize("kern", ["handheld", "iso"])
 def test_merge_x2_kernels_equal_tile_kernel(kern):
     """scale 2: the first-generation one-thread-per-LR-pixel kernel == the 16x16 HR tile kernel bit for bit; the
@@ -621,7 +577,7 @@ def test_merge_x2_kernels_equal_tile_kernel(kern):
     relative — including the fused accumulated robustness, partial (chained) launches, a frame pushed partly out of
     the image and an image that is not a tile multiple (general per-pixel body inside k_merge_x2)."""
     H, W, ts = 72, 104, 16
-    ref, fr = _frames(H, W, 4, ts, 77, base_config(ts=ts, scale=2))
+    ref, fr = merge_frames(H, W, 4, ts, 77, base_config(ts=ts, scale=2))
     fr[1] = (fr[1][0], fr[1][1] + 9.5, fr[1][2], fr[1][3])  # a frame pushed partly out of the image
     cfa = [[2, 1], [1, 0]]
     tf = [tuple(T(a) for a in f) for f in fr]
@@ -690,7 +646,7 @@ def test_merge_x3_kernel_equals_tile_kernel(kern):
     pixel), 2e-5 relative — fused accumulated robustness, chained launches, a frame pushed partly out of the image, an
     image that is not a tile multiple (generic per-pixel path inside k_merge_xs), fused local minimum, row slabs."""
     H, W, ts = 80, 112, 16
-    ref, fr = _frames(H, W, 4, ts, 78, base_config(ts=ts, scale=3))
+    ref, fr = merge_frames(H, W, 4, ts, 78, base_config(ts=ts, scale=3))
     fr[1] = (fr[1][0], fr[1][1] + 9.5, fr[1][2], fr[1][3])
     fr[2] = (fr[2][0], (fr[2][1] - 0.1).astype(np.float32), fr[2][2], fr[2][3])  # small negative flows too
     cfa = [[2, 1], [1, 0]]
@@ -751,7 +707,7 @@ def test_merge_border_bands_float64_chain():
     for scale in (2, 3, 1.5):
         c64 = base_config(ts=ts, scale=scale)
         c64.hip = {"weight_fp64": True}
-        ref, fr = _frames(H, W, 3, ts, 5, c64)
+        ref, fr = merge_frames(H, W, 3, ts, 5, c64)
         tf = [tuple(T(a) for a in f) for f in fr]
         rc = T(oracle.estimate_kernels(ref, c64))
         sH, sW = round(scale * H), round(scale * W)
@@ -780,7 +736,7 @@ def test_merge_integer_scale_geometry_decisions(scale):
     H, W, ts = 48, 64, 16
     c64 = base_config(ts=ts, scale=scale)
     c64.hip = {"weight_fp64": True}
-    ref, fr = _frames(H, W, 2, ts, 9, c64)
+    ref, fr = merge_frames(H, W, 2, ts, 9, c64)
     # adversarial flows: k + threshold +- 1 ulp for every remainder class, both signs
     thr = sorted({(2 * scale - 2 * rem - 1) / (2 * scale) for rem in range(scale)} | {0.0, 0.5})
     vals = []
@@ -850,7 +806,7 @@ def test_merge_burst_more_frames_than_one_launch_holds():
 def test_merge_burst_equals_sequential(scale):
     H, W, ts = 64, 96, 16
     cfg = base_config(ts=ts, scale=scale)
-    ref, fr = _frames(H, W, 3, ts, 31, cfg)
+    ref, fr = merge_frames(H, W, 3, ts, 31, cfg)
     cfa = [[0, 1], [1, 2]]
     oh, ow = scale * H, scale * W
     num, den = torch.zeros(oh, ow, 3, device=DEV), torch.zeros(oh, ow, 3, device=DEV)
@@ -2835,7 +2791,7 @@ def test_merge_x3_edge_frames_all_sides(kern):
     memory).  Every perimeter tile of the image takes the EDGE path for the reference frame."""
     H, W, ts = 96, 112, 16
     ny, nx = H // ts, W // ts
-    ref, fr = _frames(H, W, 8, ts, 91, base_config(ts=ts, scale=3))
+    ref, fr = merge_frames(H, W, 8, ts, 91, base_config(ts=ts, scale=3))
     rng = np.random.default_rng(5)
     flows = [np.full((ny, nx, 2), v, np.float32) for v in ((20.25, 0.4), (-20.25, -0.4), (0.3, 19.6), (-0.3, -19.6),
                                                              (-13.3, 7.7), (-40.0, 0.0))]

@@ -9,7 +9,7 @@ import test_hip_parity as t
 scale = 3
 H, W, ts = 48, 64, 16
 c64 = base_config(ts=ts, scale=scale); c64.hip = {"weight_fp64": True}
-ref, fr = t._frames(H, W, 2, ts, 9, c64)
+ref, fr = t.merge_frames(H, W, 2, ts, 9, c64)
 thr = sorted({(2 * scale - 2 * rem - 1) / (2 * scale) for rem in range(scale)} | {0.0, 0.5})
 vals = []
 for k in (-3.0, -1.0, 0.0, 2.0):
