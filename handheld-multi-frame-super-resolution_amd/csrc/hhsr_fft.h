@@ -27,8 +27,17 @@ struct HhsrFft {
     size_t tstride = 0;
     int static_rows = 0, static_cols = 0;  // > 0: the row / column kernels run the passes of this compile-time plan
                                            // (hhsr_fft.hip: HHSR_STATIC_ROWS / HHSR_STATIC_COLS)
+    bool prime_rows = false, prime_cols = false;  // the schedule holds a radix of 11, 13, 17 or 19: the run-time passes are
+                                                  // those of the kernels instantiated with them (hhsr_fft.hip: PrimePlan)
+    int rows_per_cu = 0;            // resident workgroups per CU the row kernels are built for (their persistent grid)
 };
 
+// The host half of hhsr_fft_create: which kernels would transform H x W and with what schedule (every field above but the
+// device buffers).  No HIP call.  false: sizes unsupported.
+bool hhsr_fft_schedule(HhsrFft& f, int H, int W, int batch);
+// Radix schedule of `nb` simultaneous n-point transforms in one workgroup of `nt` threads: the number of passes, their
+// radices in radices[0 .. cap); 0: none.  No HIP call.
+int hhsr_fft_radices(int n, int nb, int nt, int* radices, int cap);
 bool hhsr_fft_create(HhsrFft& f, int H, int W, int batch);   // false: sizes unsupported (caller uses the library plans)
 void hhsr_fft_destroy(HhsrFft& f);
 // n frames: one launch per phase for every f.batch of them (row blocks of all frames walked by one resident round of workgroups)

@@ -3,7 +3,8 @@
 // The library route (hhsr_grey.hip) spends 9 full passes over the image per frame (row FFT, real-FFT
 // post-processing + transpose, column FFT, transpose, mask, and the same backwards).  The mask keeps only
 // |kx| <= W/4, |ky| <= H/4, so this file does the round trip in THREE kernels, each keeping a whole 1-D
-// transform in LDS (in-place Stockham passes through registers, radices 2..16, per-pass twiddles from an LDS table):
+// transform in LDS (in-place Stockham passes through registers, radices 2..16 and the primes 11, 13, 17, 19, per-pass
+// twiddles from an LDS table):
 //   k_rows_fwd   2 rows per workgroup (simultaneously): real row -> half-length complex FFT -> real-FFT
 //                post-processing; only the Wk = W/4 + 1 kept x-bins are written, blocked-transposed
 //                (x-bins in blocks of 8, 64-byte runs);
@@ -16,8 +17,12 @@
 // The kernels are bound by the latency of their barrier phases, not by HBM: composite radices (4 passes for 2000
 // and 3000 points instead of 5 and 6) and in-place passes (half the LDS: 3 / 2 resident workgroups per CU for the
 // row / column kernels instead of 2 / 1) brought them from 171 us.
-// Supported when W is even and W/2 and H factor into {2, 3, 5, 7} and the LDS budgets fit; the caller falls
-// back to the library plans otherwise.  Numerics: float32 butterflies, float64-computed twiddle tables.
+// Supported when W is even, W/2 and H have no prime factor above 19 and a schedule fits the thread and LDS budgets
+// (hhsr_fft_schedule, host only: include/hhsr.h hhsr_grey_plan_query); the caller falls back to the library plans
+// otherwise (a factor >= 23, e.g. 3472 = 2^4 7 31; 6936 = 17 17 24).  Lengths with a factor 11 .. 19 — 4080-, 5472-, 6240-,
+// 8160-pixel rows, 3648-, 4160-, 6120-pixel columns — run kernels of their own (PrimePlan, or a compile-time plan); measured
+// at 3072 x 4080 / 3648 x 5472: 66 / 117 us per frame (library plans: 217 / 1247 us).
+// Numerics: float32 butterflies, float64-computed twiddle tables.
 #include "hhsr_common.h"
 #include "hhsr_fft.h"
 #include <math.h>
@@ -92,6 +97,10 @@ __device__ __forceinline__ void stockham_pass(float2* __restrict__ buf, int bstr
 
 // Forward FFTs, in place, of NB length-N sequences (sequence b at buf + b*bstride).  Every thread of the
 // workgroup calls it; it starts and ends with a barrier.
+// PR: also the prime radices 11, 13, 17, 19 — instantiations of their own (PrimePlan below), which the host picks only for a
+// schedule that holds one: four more arms in the switch of the 7-smooth kernels cost them registers (k_rows_fwd<1, 256>
+// 83 -> 96 VGPRs and 16 B of scratch, k_cols<2> a wave per SIMD) for radices that their lengths can never have.
+template <bool PR>
 __device__ __forceinline__ void fft_lds(float2* buf, int bstride, int NB, const float2* tw, int N,
                                         const HhsrRadices& rad, int tid, int nt) {
     int Ns = 1, toff = 0;
@@ -107,8 +116,15 @@ __device__ __forceinline__ void fft_lds(float2* buf, int bstride, int NB, const 
 #define HHSR_PASS(RR) case RR: stockham_pass<RR>(buf, bstride, NB, tw + toff, Np, Ns, tid, nt, pw); break;
             HHSR_PASS(2) HHSR_PASS(3) HHSR_PASS(4) HHSR_PASS(5) HHSR_PASS(6) HHSR_PASS(7) HHSR_PASS(8) HHSR_PASS(9)
             HHSR_PASS(10) HHSR_PASS(12) HHSR_PASS(14) HHSR_PASS(15) HHSR_PASS(16)
+            default:  // the host only schedules the radices above
+                if constexpr (PR) {
+                    switch (R) {
+                        HHSR_PASS(11) HHSR_PASS(13) HHSR_PASS(17) HHSR_PASS(19)
+                        default: break;
+                    }
+                }
+                break;
 #undef HHSR_PASS
-            default: break;  // the host only schedules the radices above
         }
         toff += pw ? Ns : (R - 1) * Ns;
         Ns *= R;
@@ -138,6 +154,11 @@ struct SPlan {
         for (int i = 0; i < p; ++i) o += pw(i) ? ns(i) : (R[i] - 1) * ns(i);
         return o;
     }
+    static constexpr int rmax() {
+        int m = 0;
+        for (int i = 0; i < NP; ++i) m = R[i] > m ? R[i] : m;
+        return m;
+    }
     static bool matches(int n, const HhsrRadices& rad) {
         if (n != N || rad.n != NP || rad.pow_min != HHSR_FFT_POW_MIN) return false;
         for (int i = 0; i < NP; ++i)
@@ -145,13 +166,20 @@ struct SPlan {
         return true;
     }
 };
-struct NoPlan {
+struct NoPlan {  // run-time passes, radices 2 .. 16
     static constexpr int N = 0;
+    static constexpr int rmax() { return 16; }
 };
+struct PrimePlan {  // run-time passes, the same radices and 11, 13, 17, 19
+    static constexpr int N = 0;
+    static constexpr int rmax() { return 19; }
+};
+template <class SP>
+constexpr bool plan_runtime = std::is_same<SP, NoPlan>::value || std::is_same<SP, PrimePlan>::value;
 // the transform length as the kernel sees it: the plan's constant, or the run-time argument
 template <class SP>
 __device__ __forceinline__ int plan_len(int runtime) {
-    return std::is_same<SP, NoPlan>::value ? runtime : SP::N;
+    return plan_runtime<SP> ? runtime : SP::N;
 }
 
 template <int N, int NB, int NT, int R, int Ns, bool PW>
@@ -212,11 +240,14 @@ __device__ __forceinline__ void fft_lds_s(float2* buf, const float2* tw, int tid
 #define HHSR_STATIC_ROWS(X)                                                                 \
     X(1, 2000, 1, FFT_NT_SMALL, 10, 10, 10, 2) /* 4000-pixel rows (12 MP 4:3) */             \
     X(2, 4000, 1, FFT_NT, 10, 10, 10, 4)       /* 8000-pixel rows (48 MP) */                 \
-    X(3, 2016, 1, FFT_NT_SMALL, 14, 12, 12)    /* 4032-pixel rows (the common 12 MP sensor) */
+    X(3, 2016, 1, FFT_NT_SMALL, 14, 12, 12)    /* 4032-pixel rows (the common 12 MP sensor) */ \
+    X(4, 2040, 1, FFT_NT_SMALL, 17, 15, 8)     /* 4080-pixel rows (12.5 MP binned 50 MP sensors) */ \
+    X(5, 2736, 2, FFT_NT, 19, 16, 9)           /* 5472-pixel rows (20 MP 3:2) */
 #define HHSR_STATIC_COLS(X)                                                                 \
     X(1, 3000, 2, FFT_NT, 3, 10, 10, 10)       /* 3000-pixel columns */                      \
     X(2, 6000, 1, FFT_NT, 10, 10, 10, 6)       /* 6000-pixel columns */                      \
-    X(3, 3024, 2, FFT_NT, 9, 8, 7, 6)          /* 3024-pixel columns */
+    X(3, 3024, 2, FFT_NT, 9, 8, 7, 6)          /* 3024-pixel columns */                      \
+    X(4, 3648, 2, FFT_NT, 19, 16, 12)          /* 3648-pixel columns */
 
 __device__ __forceinline__ bool fft_kept(int u, int n) {
     int i = u + n / 2;
@@ -250,6 +281,18 @@ constexpr int FFT_NT_SMALL = 256;
 // row kernels: 512 threads, 48 KB of LDS -> three workgroups per CU need <= 85 VGPRs (6 waves per SIMD);
 //              256 threads, 32 KB -> five workgroups per CU = 5 waves per SIMD (<= 102 VGPRs)
 __host__ __device__ constexpr int fft_rows_wpe(int nt) { return nt == FFT_NT ? 6 : 5; }
+// A radix-19 butterfly (38 data registers, as many sums and differences) does not fit 80 VGPRs: the 512-thread row kernels
+// that may run one are built for two workgroups per CU (128 VGPRs) — which is what the LDS of the lengths that get radix 19
+// in a row PAIR allows anyway (2736 points: 65 KB).
+// 256 threads, a radix 17 / 19 pass: built for, and launched as, four workgroups per CU (rows_per_cu: the persistent grid).
+// The run-time-plan kernel with all seventeen radices in its switch spills 16 - 24 bytes per lane at five (96 VGPRs; 100 / 104
+// and no scratch at four).  The 2040-point plan needs 79 / 87 VGPRs either way and is FASTER as a grid of four per CU: 66.5
+// against 76.2 us per 3072 x 4080 frame — a radix-17 pass keeps 120 of 256 threads busy, and the fifth workgroup's phases add
+// more LDS / barrier contention than they hide (profiles/fft_prime_radices.txt).
+template <int NT, class SP>
+__host__ __device__ constexpr int fft_rows_wpe_of() {
+    return (NT == FFT_NT ? SP::rmax() > 17 : SP::rmax() > 16) ? 4 : fft_rows_wpe(NT);
+}
 constexpr int FFT_COLS_WPE = 4;     // column kernel: 72 KB of LDS -> two workgroups per CU (<= 128 VGPRs)
 
 // n elements global -> LDS (or any load / store pair) with the loads of a 4-iteration batch all in flight before the first
@@ -317,7 +360,7 @@ struct FftFrames {
 };
 
 template <int RB, int NT, class SP = NoPlan>
-__global__ void __launch_bounds__(NT, fft_rows_wpe(NT)) k_rows_fwd(FftFrames fr, int H, int W,
+__global__ void __launch_bounds__(NT, (fft_rows_wpe_of<NT, SP>())) k_rows_fwd(FftFrames fr, int H, int W,
                                                                         float2* __restrict__ Tall, int Wk, HhsrRadices rad,
                                                                         const float2* __restrict__ twM, int twlen,
                                                                         const float2* __restrict__ twW) {
@@ -353,7 +396,7 @@ __global__ void __launch_bounds__(NT, fft_rows_wpe(NT)) k_rows_fwd(FftFrames fr,
             buf[rb * M + n] = reinterpret_cast<const float2*>(src + (size_t)(y0 + rb) * W)[n];
         }
     }
-    if constexpr (std::is_same<SP, NoPlan>::value) fft_lds(buf, M, nrows, tw, M, rad, tid, NT);
+    if constexpr (plan_runtime<SP>) fft_lds<std::is_same<SP, PrimePlan>::value>(buf, M, nrows, tw, M, rad, tid, NT);
     else fft_lds_s<SP, RB, NT>(buf, tw, tid);  // (RB = 1: nrows is always RB)
     // X[k] = 1/2 [(Z[k] + conj Z[M-k]) - i w_k (Z[k] - conj Z[M-k])],  w_k = exp(-2 pi i k / W); kept bins only,
     // straight from LDS to the blocked-transposed spectrum
@@ -417,7 +460,7 @@ __global__ void __launch_bounds__(FFT_NT, FFT_COLS_WPE) k_cols(float2* __restric
     } else {
         batched_for<float2>(H, tid, [&](int k) { return colb[(size_t)TB * k]; }, [&](int k, float2 v) { buf[k] = v; });
     }
-    if constexpr (std::is_same<SP, NoPlan>::value) fft_lds(buf, H, NC, tw, H, rad, tid, FFT_NT);
+    if constexpr (plan_runtime<SP>) fft_lds<std::is_same<SP, PrimePlan>::value>(buf, H, NC, tw, H, rad, tid, FFT_NT);
     else fft_lds_s<SP, NC, FFT_NT>(buf, tw, tid);
     {
         // fft_kept(u, H) with its constants hoisted: the shifted index of u lies in [lo, hi)
@@ -439,7 +482,7 @@ __global__ void __launch_bounds__(FFT_NT, FFT_COLS_WPE) k_cols(float2* __restric
             }
         }
     }
-    if constexpr (std::is_same<SP, NoPlan>::value) fft_lds(buf, H, NC, tw, H, rad, tid, FFT_NT);
+    if constexpr (plan_runtime<SP>) fft_lds<std::is_same<SP, PrimePlan>::value>(buf, H, NC, tw, H, rad, tid, FFT_NT);
     else fft_lds_s<SP, NC, FFT_NT>(buf, tw, tid);
     for (int y = tid; y < H; y += FFT_NT) {
         if (NC == 2) {
@@ -452,7 +495,7 @@ __global__ void __launch_bounds__(FFT_NT, FFT_COLS_WPE) k_cols(float2* __restric
 }
 
 template <int RB, int NT, class SP = NoPlan>
-__global__ void __launch_bounds__(NT, fft_rows_wpe(NT)) k_rows_inv(const float2* __restrict__ Tall, int H, int W, int Wk,
+__global__ void __launch_bounds__(NT, (fft_rows_wpe_of<NT, SP>())) k_rows_inv(const float2* __restrict__ Tall, int H, int W, int Wk,
                                                                         FftFrames fr, HhsrRadices rad,
                                                                         const float2* __restrict__ twM, int twlen,
                                                                         const float2* __restrict__ twW) {
@@ -523,7 +566,7 @@ __global__ void __launch_bounds__(NT, fft_rows_wpe(NT)) k_rows_inv(const float2*
             buf[rb * M + mk] = cconj(cscale(cadd(s, d), 0.5f));
         }
     }
-    if constexpr (std::is_same<SP, NoPlan>::value) fft_lds(buf, M, nrows, tw, M, rad, tid, NT);
+    if constexpr (plan_runtime<SP>) fft_lds<std::is_same<SP, PrimePlan>::value>(buf, M, nrows, tw, M, rad, tid, NT);
     else fft_lds_s<SP, RB, NT>(buf, tw, tid);
     if ((M & 1) == 0 && (W & 3) == 0) {
         const int Mh = M / 2;
@@ -549,8 +592,9 @@ static std::vector<float2> pass_twiddles(const HhsrRadices& rad);
 
 // Radix schedule: fewest passes over the supported radices, then the smallest maximum radix (registers, idle
 // lanes), then an odd / small first radix (the Ns = 1 pass stores with stride R: even R collide on LDS banks).
-// factorize caps the radix at 16.
-static const int k_radices[] = {16, 15, 14, 12, 10, 9, 8, 7, 6, 5, 4, 3, 2};
+// factorize caps the radix at 19.  The primes 11 .. 19 never divide a 7-smooth length: those keep their schedules
+// (tests/test_fft_schedule.py pins them) and their kernels (NoPlan); a schedule with one runs the PrimePlan kernels.
+static const int k_radices[] = {19, 17, 16, 15, 14, 13, 12, 11, 10, 9, 8, 7, 6, 5, 4, 3, 2};
 
 static void radix_search(int n, int rmax, int cap, int nt, int depth, int* cur, int& best_n, int* best, int& best_max) {
     if (n == 1) {
@@ -575,7 +619,7 @@ static void radix_search(int n, int rmax, int cap, int nt, int depth, int* cur, 
 
 // nb: sequences transformed together by one workgroup of nt threads (every pass runs nb * n / R butterflies)
 static bool factorize(int n, int nb, HhsrRadices& out, int nt = FFT_NT) {
-    const int rmax = 16;  // (radix 20 / 25 butterflies would exceed the 128-VGPR budget)
+    const int rmax = 19;  // (radix 20 / 25 butterflies would exceed the 128-VGPR budget)
     int cur[HHSR_MAX_RADICES], best[HHSR_MAX_RADICES], best_n = HHSR_MAX_RADICES + 1, best_max = 1 << 30;
     radix_search(n, rmax, nb * n, nt, 0, cur, best_n, best, best_max);
     if (best_n > HHSR_MAX_RADICES) return false;
@@ -663,7 +707,32 @@ static int pick_rb(int M, HhsrRadices& rad, int& nt) {
     return 0;
 }
 
-bool hhsr_fft_create(HhsrFft& f, int H, int W, int batch) {
+// resident workgroups per CU that the row kernels of this schedule are built for (fft_rows_wpe_of)
+static int rows_per_cu(const HhsrFft& f) {
+    int wpe = 0;  // waves per SIMD -> workgroups of nt_rows / 64 waves on the CU's 4 SIMDs
+#define HHSR_ROWS_CU(ID, N, RB, NT, ...) \
+    if (f.static_rows == ID) wpe = fft_rows_wpe_of<NT, SPlan<N, __VA_ARGS__>>();
+    HHSR_STATIC_ROWS(HHSR_ROWS_CU)
+#undef HHSR_ROWS_CU
+    if (!wpe && f.nt_rows == FFT_NT_SMALL) wpe = f.prime_rows ? fft_rows_wpe_of<FFT_NT_SMALL, PrimePlan>() : fft_rows_wpe(FFT_NT_SMALL);
+    if (!wpe) wpe = f.prime_rows ? fft_rows_wpe_of<FFT_NT, PrimePlan>() : fft_rows_wpe(FFT_NT);
+    return wpe * 256 / f.nt_rows;
+}
+
+static bool has_prime_radix(const HhsrRadices& rad) {
+    for (int i = 0; i < rad.n; ++i)
+        if (rad.r[i] == 11 || rad.r[i] == 13 || rad.r[i] > 16) return true;
+    return false;
+}
+
+int hhsr_fft_radices(int n, int nb, int nt, int* radices, int cap) {
+    HhsrRadices rad{};
+    if (n < 1 || nb < 1 || nt < 1 || !factorize(n, nb, rad, nt)) return 0;
+    for (int i = 0; i < rad.n && i < cap; ++i) radices[i] = rad.r[i];
+    return rad.n;
+}
+
+bool hhsr_fft_schedule(HhsrFft& f, int H, int W, int batch) {
     f = HhsrFft();
     if (batch < 1 || batch > HHSR_MAX_BATCH) return false;
     if (W % 2 || H < 2 || W < 4) return false;
@@ -683,52 +752,85 @@ bool hhsr_fft_create(HhsrFft& f, int H, int W, int batch) {
     f.H = H;
     f.W = W;
     f.Wk = Wk;
-    const std::vector<float2> hM = pass_twiddles(f.radM), hH = pass_twiddles(f.radH);
-    f.twlenM = (int)hM.size();
-    f.twlenH = (int)hH.size();
+    f.twlenM = (int)pass_twiddles(f.radM).size();
+    f.twlenH = (int)pass_twiddles(f.radH).size();
     f.lds_rows = sizeof(float2) * ((size_t)((f.twlenM + 1) & ~1) + (size_t)f.rb * M);
     f.lds_cols = sizeof(float2) * ((size_t)((f.twlenH + 1) & ~1) + (size_t)f.nc * H);
     if (f.lds_cols > 150 * 1024 || f.lds_rows > 150 * 1024) return false;
-    const bool small = f.nt_rows == FFT_NT_SMALL;  // (only with rb = 1)
-    const void* kf = small ? (const void*)k_rows_fwd<1, FFT_NT_SMALL> : f.rb == 4 ? (const void*)k_rows_fwd<4, FFT_NT>
-                   : f.rb == 2 ? (const void*)k_rows_fwd<2, FFT_NT> : (const void*)k_rows_fwd<1, FFT_NT>;
-    const void* ki = small ? (const void*)k_rows_inv<1, FFT_NT_SMALL> : f.rb == 4 ? (const void*)k_rows_inv<4, FFT_NT>
-                   : f.rb == 2 ? (const void*)k_rows_inv<2, FFT_NT> : (const void*)k_rows_inv<1, FFT_NT>;
-    if (hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_rows) != hipSuccess ||
-        hipFuncSetAttribute(ki, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_rows) != hipSuccess ||
-        hipFuncSetAttribute(f.nc == 2 ? (const void*)k_cols<2> : (const void*)k_cols<1>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_cols) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    f.twM = upload(hM);
-    f.twH = upload(hH);
-    f.twW = upload(plain_twiddles(M, (double)W));  // exp(-2 pi i k / W), k < M
     f.batch = batch;
     f.tstride = (size_t)((Wk + 7) / 8) * 8 * H;  // one spectrum per frame of a batch
-    if (hipMalloc((void**)&f.T, sizeof(float2) * f.tstride * batch) != hipSuccess) f.T = nullptr;
-    if (!f.twM || !f.twH || !f.twW || !f.T) {
-        hhsr_fft_destroy(f);
-        return false;
-    }
+    f.prime_rows = has_prime_radix(f.radM);
+    f.prime_cols = has_prime_radix(f.radH);
     // static plans (HHSR_FFT_STATIC: bit 0 rows, bit 1 columns; 0: tests / A-B run the run-time passes)
     const char* es = getenv("HHSR_FFT_STATIC");
     const int allow = es ? atoi(es) : 3;
     f.static_rows = f.static_cols = 0;
 #define HHSR_TRY_ROWS(ID, N, RB, NT, ...)                                                                                    \
-    if ((allow & 1) && !f.static_rows && f.rb == RB && f.nt_rows == NT && SPlan<N, __VA_ARGS__>::matches(M, f.radM) &&       \
-        hipFuncSetAttribute((const void*)k_rows_fwd<RB, NT, SPlan<N, __VA_ARGS__>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_rows) == hipSuccess && \
-        hipFuncSetAttribute((const void*)k_rows_inv<RB, NT, SPlan<N, __VA_ARGS__>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_rows) == hipSuccess)   \
+    if ((allow & 1) && !f.static_rows && f.rb == RB && f.nt_rows == NT && SPlan<N, __VA_ARGS__>::matches(M, f.radM))         \
         f.static_rows = ID;
     HHSR_STATIC_ROWS(HHSR_TRY_ROWS)
 #undef HHSR_TRY_ROWS
 #define HHSR_TRY_COLS(ID, N, NC, NT, ...)                                                                                    \
-    if ((allow & 2) && !f.static_cols && f.nc == NC && SPlan<N, __VA_ARGS__>::matches(H, f.radH) &&                          \
-        hipFuncSetAttribute((const void*)k_cols<NC, SPlan<N, __VA_ARGS__>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_cols) == hipSuccess) \
-        f.static_cols = ID;
+    if ((allow & 2) && !f.static_cols && f.nc == NC && SPlan<N, __VA_ARGS__>::matches(H, f.radH)) f.static_cols = ID;
+    HHSR_STATIC_COLS(HHSR_TRY_COLS)
+#undef HHSR_TRY_COLS
+    f.rows_per_cu = rows_per_cu(f);
+    return true;
+}
+
+// the run-time-plan kernels of a schedule (7-smooth schedules: the NoPlan instantiations; PrimePlan otherwise)
+template <class RP>
+static const void* rows_fwd_kernel(const HhsrFft& f) {
+    return f.nt_rows == FFT_NT_SMALL ? (const void*)k_rows_fwd<1, FFT_NT_SMALL, RP> : f.rb == 4 ? (const void*)k_rows_fwd<4, FFT_NT, RP>
+         : f.rb == 2 ? (const void*)k_rows_fwd<2, FFT_NT, RP> : (const void*)k_rows_fwd<1, FFT_NT, RP>;
+}
+template <class RP>
+static const void* rows_inv_kernel(const HhsrFft& f) {
+    return f.nt_rows == FFT_NT_SMALL ? (const void*)k_rows_inv<1, FFT_NT_SMALL, RP> : f.rb == 4 ? (const void*)k_rows_inv<4, FFT_NT, RP>
+         : f.rb == 2 ? (const void*)k_rows_inv<2, FFT_NT, RP> : (const void*)k_rows_inv<1, FFT_NT, RP>;
+}
+
+bool hhsr_fft_create(HhsrFft& f, int H, int W, int batch) {
+    if (!hhsr_fft_schedule(f, H, W, batch)) {
+        f = HhsrFft();
+        return false;
+    }
+    const int M = W / 2;
+    const void* kf = f.prime_rows ? rows_fwd_kernel<PrimePlan>(f) : rows_fwd_kernel<NoPlan>(f);
+    const void* ki = f.prime_rows ? rows_inv_kernel<PrimePlan>(f) : rows_inv_kernel<NoPlan>(f);
+    const void* kc = f.prime_cols ? (f.nc == 2 ? (const void*)k_cols<2, PrimePlan> : (const void*)k_cols<1, PrimePlan>)
+                                  : (f.nc == 2 ? (const void*)k_cols<2> : (const void*)k_cols<1>);
+    if (hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_rows) != hipSuccess ||
+        hipFuncSetAttribute(ki, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_rows) != hipSuccess ||
+        hipFuncSetAttribute(kc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_cols) != hipSuccess) {
+        (void)hipGetLastError();
+        f = HhsrFft();
+        return false;
+    }
+    f.twM = upload(pass_twiddles(f.radM));
+    f.twH = upload(pass_twiddles(f.radH));
+    f.twW = upload(plain_twiddles(M, (double)W));  // exp(-2 pi i k / W), k < M
+    if (hipMalloc((void**)&f.T, sizeof(float2) * f.tstride * batch) != hipSuccess) f.T = nullptr;
+    if (!f.twM || !f.twH || !f.twW || !f.T) {
+        hhsr_fft_destroy(f);
+        return false;
+    }
+    // the static plan's kernels need the same attribute; one that cannot have it leaves the run-time passes in place
+#define HHSR_TRY_ROWS(ID, N, RB, NT, ...)                                                                                    \
+    if (f.static_rows == ID &&                                                                                                \
+        (hipFuncSetAttribute((const void*)k_rows_fwd<RB, NT, SPlan<N, __VA_ARGS__>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_rows) != hipSuccess || \
+         hipFuncSetAttribute((const void*)k_rows_inv<RB, NT, SPlan<N, __VA_ARGS__>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_rows) != hipSuccess))  \
+        f.static_rows = 0;
+    HHSR_STATIC_ROWS(HHSR_TRY_ROWS)
+#undef HHSR_TRY_ROWS
+#define HHSR_TRY_COLS(ID, N, NC, NT, ...)                                                                                    \
+    if (f.static_cols == ID &&                                                                                                \
+        hipFuncSetAttribute((const void*)k_cols<NC, SPlan<N, __VA_ARGS__>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_cols) != hipSuccess) \
+        f.static_cols = 0;
     HHSR_STATIC_COLS(HHSR_TRY_COLS)
 #undef HHSR_TRY_COLS
     (void)hipGetLastError();
+    f.rows_per_cu = rows_per_cu(f);
     f.ok = true;
     return true;
 }
@@ -745,7 +847,7 @@ int hhsr_fft_lowpass(const HhsrFft& f, const float* const* srcs, float* const* d
     // row kernels: at most one resident round of workgroups (3 per CU by their 48 kB of LDS, 5 per CU for the 256-thread
     // single-row workgroups with 32 kB), each walking several blocks
     const bool small = f.nt_rows == FFT_NT_SMALL;
-    const int persist = small ? 1280 : 768;
+    const int persist = 256 * f.rows_per_cu;  // (7-smooth schedules: 1280 / 768)
     // unnormalised inverse transforms multiply by (W/2) and H
     const float norm = (float)(1.0 / ((double)(f.W / 2) * (double)f.H));
     // Frames per round: the kept spectra of a round's frames live between the three kernels, and they should live in the
@@ -765,9 +867,9 @@ int hhsr_fft_lowpass(const HhsrFft& f, const float* const* srcs, float* const* d
         }
         const int nrb_all = hhsr_cdiv(f.H, f.rb) * fr.n;
         const int nrb = persist > 0 && persist < nrb_all ? persist : nrb_all;
-#define ROWS_FWD(RB, NT) hipLaunchKernelGGL((k_rows_fwd<RB, NT>), dim3(nrb), dim3(NT), f.lds_rows, s, fr, f.H, f.W, f.T, f.Wk, \
+#define ROWS_FWD(RB, NT) hipLaunchKernelGGL((k_rows_fwd<RB, NT, RP>), dim3(nrb), dim3(NT), f.lds_rows, s, fr, f.H, f.W, f.T, f.Wk, \
                                             f.radM, f.twM, f.twlenM, f.twW)
-#define ROWS_INV(RB, NT) hipLaunchKernelGGL((k_rows_inv<RB, NT>), dim3(nrb), dim3(NT), f.lds_rows, s, f.T, f.H, f.W, f.Wk, fr, \
+#define ROWS_INV(RB, NT) hipLaunchKernelGGL((k_rows_inv<RB, NT, RP>), dim3(nrb), dim3(NT), f.lds_rows, s, f.T, f.H, f.W, f.Wk, fr, \
                                             f.radM, f.twM, f.twlenM, f.twW)
 #define HHSR_RUN_ROWS_FWD(ID, N, RB, NT, ...)                                                                                \
         if (f.static_rows == ID)                                                                                              \
@@ -776,8 +878,15 @@ int hhsr_fft_lowpass(const HhsrFft& f, const float* const* srcs, float* const* d
         else
         HHSR_STATIC_ROWS(HHSR_RUN_ROWS_FWD)
 #undef HHSR_RUN_ROWS_FWD
-        if (small) ROWS_FWD(1, FFT_NT_SMALL); else if (f.rb == 4) ROWS_FWD(4, FFT_NT); else if (f.rb == 2) ROWS_FWD(2, FFT_NT);
-        else ROWS_FWD(1, FFT_NT);
+        if (f.prime_rows) {
+            using RP = PrimePlan;
+            if (small) ROWS_FWD(1, FFT_NT_SMALL); else if (f.rb == 4) ROWS_FWD(4, FFT_NT); else if (f.rb == 2) ROWS_FWD(2, FFT_NT);
+            else ROWS_FWD(1, FFT_NT);
+        } else {
+            using RP = NoPlan;
+            if (small) ROWS_FWD(1, FFT_NT_SMALL); else if (f.rb == 4) ROWS_FWD(4, FFT_NT); else if (f.rb == 2) ROWS_FWD(2, FFT_NT);
+            else ROWS_FWD(1, FFT_NT);
+        }
 #define HHSR_RUN_COLS(ID, N, NC, NT, ...)                                                                                    \
         if (f.static_cols == ID)                                                                                              \
             hipLaunchKernelGGL((k_cols<NC, SPlan<N, __VA_ARGS__>>), dim3(((f.Wk + 63) / 64) * (64 / NC), fr.n), dim3(NT), f.lds_cols, \
@@ -785,12 +894,11 @@ int hhsr_fft_lowpass(const HhsrFft& f, const float* const* srcs, float* const* d
         else
         HHSR_STATIC_COLS(HHSR_RUN_COLS)
 #undef HHSR_RUN_COLS
-        if (f.nc == 2)
-            hipLaunchKernelGGL(k_cols<2>, dim3(((f.Wk + 63) / 64) * 32, fr.n), dim3(FFT_NT), f.lds_cols, s, f.T, f.tstride,
-                               f.H, f.W, f.Wk, f.radH, f.twH, f.twlenH, norm);
-        else
-            hipLaunchKernelGGL(k_cols<1>, dim3(((f.Wk + 63) / 64) * 64, fr.n), dim3(FFT_NT), f.lds_cols, s, f.T, f.tstride,
-                               f.H, f.W, f.Wk, f.radH, f.twH, f.twlenH, norm);
+#define COLS(NC, RP) hipLaunchKernelGGL((k_cols<NC, RP>), dim3(((f.Wk + 63) / 64) * (64 / NC), fr.n), dim3(FFT_NT), f.lds_cols, s, f.T, \
+                                      f.tstride, f.H, f.W, f.Wk, f.radH, f.twH, f.twlenH, norm)
+        if (f.prime_cols) { if (f.nc == 2) COLS(2, PrimePlan); else COLS(1, PrimePlan); }
+        else { if (f.nc == 2) COLS(2, NoPlan); else COLS(1, NoPlan); }
+#undef COLS
 #define HHSR_RUN_ROWS_INV(ID, N, RB, NT, ...)                                                                                \
         if (f.static_rows == ID)                                                                                              \
             hipLaunchKernelGGL((k_rows_inv<RB, NT, SPlan<N, __VA_ARGS__>>), dim3(nrb), dim3(NT), f.lds_rows, s, f.T, f.H, f.W, f.Wk, \
@@ -798,8 +906,15 @@ int hhsr_fft_lowpass(const HhsrFft& f, const float* const* srcs, float* const* d
         else
         HHSR_STATIC_ROWS(HHSR_RUN_ROWS_INV)
 #undef HHSR_RUN_ROWS_INV
-        if (small) ROWS_INV(1, FFT_NT_SMALL); else if (f.rb == 4) ROWS_INV(4, FFT_NT); else if (f.rb == 2) ROWS_INV(2, FFT_NT);
-        else ROWS_INV(1, FFT_NT);
+        if (f.prime_rows) {
+            using RP = PrimePlan;
+            if (small) ROWS_INV(1, FFT_NT_SMALL); else if (f.rb == 4) ROWS_INV(4, FFT_NT); else if (f.rb == 2) ROWS_INV(2, FFT_NT);
+            else ROWS_INV(1, FFT_NT);
+        } else {
+            using RP = NoPlan;
+            if (small) ROWS_INV(1, FFT_NT_SMALL); else if (f.rb == 4) ROWS_INV(4, FFT_NT); else if (f.rb == 2) ROWS_INV(2, FFT_NT);
+            else ROWS_INV(1, FFT_NT);
+        }
 #undef ROWS_FWD
 #undef ROWS_INV
     }

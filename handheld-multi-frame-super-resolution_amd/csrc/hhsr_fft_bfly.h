@@ -181,3 +181,42 @@ template <> __device__ __forceinline__ void dft_reg<14>(float2* v) { dft_comp<7,
 template <> __device__ __forceinline__ void dft_reg<15>(float2* v) { dft_comp<5, 3>(v); }
 template <> __device__ __forceinline__ void dft_reg<16>(float2* v) { dft_comp<4, 4>(v); }
 
+// ---- prime radices 11, 13, 17, 19 (sensor lengths such as 2040 = 8 15 17, 2736 = 9 16 19, 3120 = 13 16 15) --------------
+// dft7's symmetric form for any odd prime P: a_j = x_j + x_{P-j}, b_j = x_j - x_{P-j} (j = 1 .. (P-1)/2);
+//   X_k, X_{P-k} = x_0 + sum_j a_j cos(2 pi j k / P) -+ i sum_j b_j sin(2 pi j k / P).
+// (P - 1)^2 multiply-adds on 2 (P - 1) sums and differences; the constants come from the constexpr table.
+template <int P>
+__device__ __forceinline__ void dft_prime(float2* v) {
+    constexpr TwTab<P> tab{};  // c[m] = cos(2 pi m / P), s[m] = -sin(2 pi m / P)
+    constexpr int Hp = (P - 1) / 2;
+    const float2 x0 = v[0];
+    float2 a[Hp], b[Hp];
+#pragma unroll
+    for (int j = 1; j <= Hp; ++j) {
+        a[j - 1] = cadd(v[j], v[P - j]);
+        b[j - 1] = csub(v[j], v[P - j]);
+    }
+    float2 dc = x0;
+#pragma unroll
+    for (int j = 0; j < Hp; ++j) dc = cadd(dc, a[j]);
+    v[0] = dc;
+#pragma unroll
+    for (int k = 1; k <= Hp; ++k) {
+        float2 m = x0, n = make_float2(0.f, 0.f);
+#pragma unroll
+        for (int j = 1; j <= Hp; ++j) {
+            const int i = (j * k) % P;
+            m.x += tab.c[i] * a[j - 1].x;
+            m.y += tab.c[i] * a[j - 1].y;
+            n.x -= tab.s[i] * b[j - 1].x;  // + sin(2 pi j k / P) b_j
+            n.y -= tab.s[i] * b[j - 1].y;
+        }
+        const float2 mn = mul_mi(n);
+        v[k] = cadd(m, mn);
+        v[P - k] = csub(m, mn);
+    }
+}
+template <> __device__ __forceinline__ void dft_reg<11>(float2* v) { dft_prime<11>(v); }
+template <> __device__ __forceinline__ void dft_reg<13>(float2* v) { dft_prime<13>(v); }
+template <> __device__ __forceinline__ void dft_reg<17>(float2* v) { dft_prime<17>(v); }
+template <> __device__ __forceinline__ void dft_reg<19>(float2* v) { dft_prime<19>(v); }

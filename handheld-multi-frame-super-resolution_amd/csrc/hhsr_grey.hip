@@ -158,6 +158,50 @@ extern "C" int hhsr_grey_plan_create(int H, int W, int flags, void** plan_out) {
     return 0;
 }
 
+// the record of hhsr_grey_plan_query / hhsr_grey_plan_info (include/hhsr.h) of a scheduled transform
+static void grey_info(const HhsrFft* f, int32_t* out, int n) {
+    for (int i = 0; i < n; ++i) out[i] = 0;
+    if (!f) return;
+    out[0] = 1;
+    out[1] = f->rb;
+    out[2] = f->nt_rows;
+    out[3] = f->nc;
+    out[4] = f->static_rows;
+    out[5] = f->static_cols;
+    out[6] = (int32_t)f->lds_rows;
+    out[7] = (int32_t)f->lds_cols;
+    out[8] = f->Wk;
+    out[9] = f->radM.n;
+    out[10] = f->radH.n;
+    for (int i = 0; i < f->radM.n && i < 16; ++i) out[16 + i] = f->radM.r[i];
+    for (int i = 0; i < f->radH.n && i < 16; ++i) out[32 + i] = f->radH.r[i];
+}
+
+extern "C" int hhsr_grey_plan_query(int H, int W, int flags, int32_t* out, int n) {
+    HHSR_ARG(out && H > 0 && W > 0 && n >= HHSR_GREY_INFO_LEN);
+    const int batch = (flags >> 8) & 0xff ? (flags >> 8) & 0xff : 1;
+    HHSR_ARG(batch <= HHSR_MAX_BATCH);
+    HhsrFft f;
+    grey_info((flags & 4) && hhsr_fft_schedule(f, H, W, batch) ? &f : nullptr, out, n);
+    return 0;
+}
+
+extern "C" int hhsr_grey_plan_info(void* plan, int32_t* out, int n) {
+    HHSR_ARG(plan && out && n >= HHSR_GREY_INFO_LEN);
+    const GreyPlan* p = static_cast<const GreyPlan*>(plan);
+    grey_info(p->fft.ok ? &p->fft : nullptr, out, n);
+    return 0;
+}
+
+extern "C" int hhsr_grey_radix_schedule(int n_points, int seqs, int threads, int32_t* out, int n) {
+    HHSR_ARG(out && n_points > 0 && seqs > 0 && threads > 0 && n >= 1 + HHSR_MAX_RADICES);
+    for (int i = 0; i < n; ++i) out[i] = 0;
+    int rad[HHSR_MAX_RADICES];
+    out[0] = hhsr_fft_radices(n_points, seqs, threads, rad, HHSR_MAX_RADICES);
+    for (int i = 0; i < out[0]; ++i) out[1 + i] = rad[i];
+    return 0;
+}
+
 extern "C" int hhsr_grey_plan_destroy(void* plan) {
     if (!plan) return 0;
     GreyPlan* p = static_cast<GreyPlan*>(plan);

@@ -18,6 +18,7 @@ U8P = C.POINTER(C.c_uint8)
 DP = C.POINTER(C.c_double)
 FP = C.POINTER(C.c_float)
 PP = C.POINTER(C.c_void_p)
+I32P = C.POINTER(C.c_int32)
 
 # name -> argtypes (all return int)
 _SIGS = {
@@ -27,6 +28,9 @@ _SIGS = {
     "hhsr_grey_lowpass": [P, P, P, P],
     "hhsr_grey_lowpass_batch": [P, PP, PP, I, P],
     "hhsr_grey_plan_destroy": [P],
+    "hhsr_grey_plan_query": [I, I, I, I32P, I],
+    "hhsr_grey_plan_info": [P, I32P, I],
+    "hhsr_grey_radix_schedule": [I, I, I, I32P, I],
     "hhsr_pad_circular": [P, I, I, I, P, I, I, I, P],
     "hhsr_gauss_decimate": [P, I, I, I, P, I, I, FP, I, P],
     "hhsr_gauss_decimate_batch": [PP, I, I, I, I, PP, I, I, FP, I, P],
@@ -70,6 +74,7 @@ MERGE_LOAD_ACC, MERGE_DO_REF, MERGE_DIVIDE, MERGE_STORE_DEN = 1, 2, 4, 8
 MERGE_LOCAL_MIN, MERGE_STORE_CLASSES, MERGE_LOAD_CLASSES = 16, 32, 64
 MAX_FRAMES = 64
 MAX_BATCH = 8  # HHSR_MAX_BATCH: frames per launch of the batched front-end entry points
+GREY_INFO_LEN = 48  # HHSR_GREY_INFO_LEN: values of the record of hhsr_grey_plan_query / hhsr_grey_plan_info
 
 _lib = None
 

@@ -73,6 +73,40 @@ def _grey_plan(H, W, device, batch=1):
     return p
 
 
+def _grey_info_dict(rec):
+    nm, nh = rec[9], rec[10]
+    return {"fused": bool(rec[0]), "rows_per_workgroup": rec[1], "row_threads": rec[2], "cols_per_workgroup": rec[3],
+            "static_rows": rec[4], "static_cols": rec[5], "lds_rows": rec[6], "lds_cols": rec[7], "kept_bins": rec[8],
+            "radices_rows": list(rec[16:16 + nm]), "radices_cols": list(rec[32:32 + nh])}
+
+
+def grey_plan_info(H, W, plan=None):
+    """Which route the "FFT" grey image of an H x W frame takes: {"fused": the in-LDS kernels (else the library plans),
+    rows / columns per workgroup, threads of the row kernels, ids of the compile-time plans (0: run-time passes), LDS bytes,
+    kept x-bins, the radix schedules of the W/2-point ("radices_rows") and H-point ("radices_cols") transforms}.  Asked of
+    the library's host side (hhsr_grey_plan_query, under the same HHSR_GREY_PLAN as a plan would be created): no GPU
+    needed.  `plan`: report this live plan (of _grey_plan) instead."""
+    import ctypes
+    import os
+
+    rec = (ctypes.c_int32 * _lib.GREY_INFO_LEN)()
+    if plan is not None:
+        _lib.call("hhsr_grey_plan_info", plan.handle, rec, _lib.GREY_INFO_LEN)
+    else:
+        _lib.call("hhsr_grey_plan_query", int(H), int(W), int(os.environ.get("HHSR_GREY_PLAN", "4")), rec,
+                  _lib.GREY_INFO_LEN)
+    return _grey_info_dict(list(rec))
+
+
+def grey_radix_schedule(n, seqs=1, threads=512):
+    """Radices of the passes that `seqs` simultaneous n-point transforms get in a workgroup of `threads` threads ([]: none)."""
+    import ctypes
+
+    rec = (ctypes.c_int32 * 17)()
+    _lib.call("hhsr_grey_radix_schedule", int(n), int(seqs), int(threads), rec, 17)
+    return list(rec[1:1 + rec[0]])
+
+
 def compute_grey_images_batch(imgs, method="FFT"):
     """compute_grey_images() of several frames of one shape: ONE launch per transform phase for up to
     _lib.MAX_BATCH frames (hhsr_grey_lowpass_batch) instead of three per frame — the per-frame launches are

@@ -58,8 +58,9 @@ int hhsr_lowpass_mask_r2c(float* spec, int H, int W, int64_t stride_y, int64_t s
  * buffer, owned by the plan); a plan is mutable state: use it from one stream at a time.
  * Returns 1000 + hipfftResult on a hipFFT error. */
 #define HHSR_GREY_PRUNED 1   /* batched row plans + strided column plans on the kept x-bins only (experiment) */
-#define HHSR_GREY_FUSED 4    /* three in-LDS kernels (rows, columns + mask, rows) when W is even and W/2, H factor
-                                into {2,3,5,7} and fit LDS; otherwise the library plans are used */
+#define HHSR_GREY_FUSED 4    /* three in-LDS kernels (rows, columns + mask, rows) when W is even, W/2 and H have no prime
+                                factor above 19 and their transforms fit the kernels' LDS and thread budgets
+                                (hhsr_grey_plan_query tells); otherwise the library plans are used */
 #define HHSR_GREY_TPRUNED 2  /* row plans with a transposed spectrum + contiguous column plans on the kept bins */
 #define HHSR_GREY_BATCH(n) ((n) << 8)  /* the plan holds n (<= HHSR_MAX_BATCH) spectra: hhsr_grey_lowpass_batch then
                                           transforms n frames with ONE launch per phase (default 1) */
@@ -70,6 +71,22 @@ int hhsr_grey_lowpass(void* plan, const float* src, float* dst, void* stream);
  * launch per phase (the per-frame launches are latency-bound: 3 x 19 launches of ~40 us per 12 MP burst). */
 int hhsr_grey_lowpass_batch(void* plan, const float* const* srcs, float* const* dsts, int n_frames, void* stream);
 int hhsr_grey_plan_destroy(void* plan);
+/* Which route a plan takes.  out (HOST, n >= HHSR_GREY_INFO_LEN values; the unused ones are 0):
+ *   [0] 1 = the fused kernels run, 0 = the library plans (every other value is 0 then)
+ *   [1] rows per workgroup and [2] threads per workgroup of the row kernels, [3] kept columns per workgroup
+ *   [4] / [5] id of the compile-time plan of the row / column kernels (0: run-time passes)
+ *   [6] / [7] LDS bytes per workgroup of the row / column kernels, [8] kept x-bins
+ *   [9] / [10] number of passes of the W/2-point / H-point transforms
+ *   [16 .. 32) the radices of the W/2-point passes, [32 .. 48) those of the H-point passes, in execution order.
+ * hhsr_grey_plan_query answers for the plan that hhsr_grey_plan_create(H, W, flags, .) WOULD build and makes no HIP
+ * call (usable without a device); hhsr_grey_plan_info reports a live plan.
+ * hhsr_grey_radix_schedule: the schedule of `seqs` simultaneous n_points-point transforms in a workgroup of `threads`
+ * threads, as the kernels' host side searches it: out[0] = number of passes (0: no schedule), out[1 ..] the radices
+ * (HOST, n >= 1 + 16 values).  No HIP call. */
+#define HHSR_GREY_INFO_LEN 48
+int hhsr_grey_plan_query(int H, int W, int flags, int32_t* out, int n);
+int hhsr_grey_plan_info(void* plan, int32_t* out, int n);
+int hhsr_grey_radix_schedule(int n_points, int seqs, int threads, int32_t* out, int n);
 
 /* ---- pyramid (alignment.py:27-37, 74-82; utils_image.py:360-391) ------------------------------ */
 /* dst[y][x] = src[y mod H][x mod W], dst is Hp x Wp (F.pad 'circular', bottom/right). */

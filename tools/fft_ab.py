@@ -19,6 +19,10 @@ ENV = os.environ.get("FFT_AB_ENV", "HHSR_FFT_STATIC")
 NF, REP = 4, 30
 dev = "cuda"
 imgs = [torch.rand((H, W), device=dev) for _ in range(NF)]
+info = utils_image.grey_plan_info(H, W)  # (as the library's host side schedules this size under the default switches)
+print(f"{H}x{W}: " + (f"fused kernels, rows {info['radices_rows']} x{info['rows_per_workgroup']} per {info['row_threads']} threads "
+                      f"(static plan {info['static_rows']}), columns {info['radices_cols']} x{info['cols_per_workgroup']} "
+                      f"(static plan {info['static_cols']})" if info["fused"] else "library plans"))
 res = {}
 for rnd in range(3):
     for m in masks:
