@@ -336,6 +336,7 @@ static void bm_launch(const float* ref, int ref_pitch, const float* mov, int mh,
 extern "C" int hhsr_bm_l2(const float* ref, int ref_pitch, const float* mov, int mh, int mw, int mov_pitch,
                           float* flow, int ny, int nx, int ts, int r, void* stream) {
     HHSR_ARG(ref && mov && flow && mh > 0 && mw > 0 && ny > 0 && nx > 0 && r >= 0);
+    HHSR_ARG(ts > 0 && (int64_t)ref_pitch >= (int64_t)nx * ts && mov_pitch >= mw);  // rows may not overlap
     HHSR_ARG(ts == 8 || ts == 16 || ts == 32 || ts == 64);  // the reference's box filters (block_matching.py:47-57)
     HHSR_ARG(bm_lds(ts, r) <= 64 * 1024);
     bm_launch<false>(ref, ref_pitch, mov, mh, mw, mov_pitch, flow, ny, nx, ts, r, 0, (hipStream_t)stream);
@@ -345,6 +346,7 @@ extern "C" int hhsr_bm_l2(const float* ref, int ref_pitch, const float* mov, int
 extern "C" int hhsr_bm_l1(const float* ref, int ref_pitch, const float* mov, int mh, int mw, int mov_pitch,
                           float* flow, int ny, int nx, int ts, int r, int mode, void* stream) {
     HHSR_ARG(ref && mov && flow && mh > 0 && mw > 0 && ny > 0 && nx > 0 && r >= 0);
+    HHSR_ARG(ts > 0 && (int64_t)ref_pitch >= (int64_t)nx * ts && mov_pitch >= mw);  // rows may not overlap
     HHSR_ARG(ts == 16 || ts == 32 || ts == 64);  // ts = 8 raises NotImplementedError upstream (block_matching.py:87)
     HHSR_ARG(mode == 0 || mode == 1);
     HHSR_ARG(bm_lds(ts, r) <= 64 * 1024);
@@ -531,6 +533,7 @@ extern "C" int hhsr_ica(const float* ref, const float* gx, const float* gy, int 
                         const float* mov, int mh, int mw, int mov_pitch, float* flow, int ny, int nx, int ts,
                         int n_iter, int flags, void* stream) {
     HHSR_ARG(ref && gx && gy && hess && mov && flow && mh > 0 && mw > 0 && ny > 0 && nx > 0 && n_iter > 0);
+    HHSR_ARG(ts > 0 && (int64_t)ref_pitch >= (int64_t)nx * ts && mov_pitch >= mw);  // rows may not overlap
     const dim3 grid(nx, ny);
     hipStream_t s = (hipStream_t)stream;
     const int bug = flags & 1;
@@ -885,6 +888,7 @@ extern "C" int hhsr_align_level_batch(const float* ref, int rh, int rw, int ref_
     HHSR_ARG(ts == 8 || ts == 16 || ts == 32);
     HHSR_ARG(metric == 0 || ts >= 16);  // block_matching.py:87: no L1 search for 8-pixel tiles
     HHSR_ARG(ny * ts <= rh && nx * ts <= rw);
+    HHSR_ARG(ref_pitch >= rw && mov_pitch >= mw);
     HHSR_ARG(r == 1 || r == 2 || r == 4);  // compiled search radii (other radii: hhsr_bm_* + hhsr_ica)
     HHSR_ARG(!coarse_flows || (cny > 0 && cnx > 0 && rep > 0));
     const size_t l = align_wave_lds(ts, r);

@@ -12,7 +12,12 @@
  *  - every pointer is a DEVICE pointer owned by the caller unless the parameter is documented as
  *    "host"; functions never allocate, free or synchronise (the hhsr_grey_plan_create/destroy pair
  *    excepted): they only enqueue work on `stream` (a hipStream_t passed as void*; NULL = null stream);
- *  - images are row-major float32; `pitch` arguments are in ELEMENTS;
+ *  - images are row-major float32; `pitch` arguments are in ELEMENTS: the distance between the starts of two rows,
+ *    >= the width (error -1 otherwise).  A pitch lets a caller pass a hipMallocPitch buffer or a window of a larger
+ *    frame without a copy: nothing between the end of a row and the start of the next is read into a result or
+ *    written.  Only the arguments that have a pitch can be padded: flows, Hessians, covariances, robustness maps,
+ *    guide statistics and every output of the merge are COMPACT whatever the raw pitch is.  Pointers need the
+ *    alignment of their element type unless an entry point says more;
  *  - flow fields are float32 [ny][nx][2] = (dx, dy) per tile, moving(p + flow) ~ ref(p);
  *  - covariances are float32 [H/2][W/2][2][2]; accumulators float32 [sH][sW][3];
  *  - the CFA is 4 bytes {c00, c01, c10, c11} with 0=R, 1=G, 2=B;
@@ -89,22 +94,27 @@ int hhsr_grey_plan_info(void* plan, int32_t* out, int n);
 int hhsr_grey_radix_schedule(int n_points, int seqs, int threads, int32_t* out, int n);
 
 /* ---- pyramid (alignment.py:27-37, 74-82; utils_image.py:360-391) ------------------------------ */
-/* dst[y][x] = src[y mod H][x mod W], dst is Hp x Wp (F.pad 'circular', bottom/right). */
+/* dst[y][x] = src[y mod H][x mod W], dst is Hp x Wp (F.pad 'circular', bottom/right); src_pitch >= W, dst_pitch >= Wp,
+ * the padding columns of dst are left as they are. */
 int hhsr_pad_circular(const float* src, int H, int W, int src_pitch,
                       float* dst, int Hp, int Wp, int dst_pitch, void* stream);
 /* Valid separable Gaussian (rows then columns) + decimation by `factor`:
- * dst is floor((H-2r)/f) x floor((W-2r)/f), r = (ntaps-1)/2; factor 2 or 4 with ntaps = 4*factor+1 (the reference's kernels).  `taps` is a HOST array. */
+ * dst is floor((H-2r)/f) x floor((W-2r)/f), r = (ntaps-1)/2; factor 2 or 4 with ntaps = 4*factor+1 (the reference's kernels).  `taps` is a HOST array.
+ * src_pitch >= W, dst_pitch >= the output width; the padding columns of dst are left as they are. */
 int hhsr_gauss_decimate(const float* src, int H, int W, int src_pitch,
                         float* dst, int dst_pitch, int factor,
                         const float* taps, int ntaps, void* stream);
-/* n_frames levels of the same shape in one launch (HOST arrays of device pointers); per frame bit-identical. */
+/* n_frames levels of the same shape in one launch (HOST arrays of device pointers; one src_pitch and one dst_pitch for all
+ * of them); per frame bit-identical. */
 int hhsr_gauss_decimate_batch(const float* const* srcs, int n_frames, int H, int W, int src_pitch,
                               float* const* dsts, int dst_pitch, int factor,
                               const float* taps, int ntaps, void* stream);
 
 /* ---- Lucas-Kanade precompute (ICA.py:15-76) ---------------------------------------------------
  * gx = I[x+1]-I[x-1], gy likewise (zero border, no 1/2 factor); hess[ty][tx] = sum over the tile of
- * [gx^2, gx gy; gx gy, gy^2] for the floor(H/ts) x floor(W/ts) tile grid. */
+ * [gx^2, gx gy; gx gy, gy^2] for the floor(H/ts) x floor(W/ts) tile grid.
+ * gx and gy are written AT THE INPUT'S PITCH (each needs H * pitch elements; their padding columns are left as they are) —
+ * the layout hhsr_ica reads them in; hess is compact. */
 int hhsr_grad_hessian(const float* lvl, int H, int W, int pitch, int ts,
                       float* gx, float* gy, float* hess, void* stream);
 
@@ -114,14 +124,18 @@ int hhsr_grad_hessian(const float* lvl, int H, int W, int pitch, int ts,
  * tile*ts + round_half_even(flow) - r with clamp-to-edge addressing of the moving level, first
  * minimum in row-major order; the shift is ADDED to the un-rounded flow.
  * L1 (mode 0): the INTENDED semantics of the reference's undefined-behaviour kernels — SAD, zero
- * outside the moving level, flow <- round(flow) + shift.  mode 1: flow <- round_half_even(flow). */
+ * outside the moving level, flow <- round(flow) + shift.  mode 1: flow <- round_half_even(flow).
+ * The reference level is ny*ts x nx*ts: ref_pitch >= nx * ts, mov_pitch >= mw (error -1 otherwise); the two pitches are
+ * independent of each other. */
 int hhsr_bm_l2(const float* ref, int ref_pitch, const float* mov, int mh, int mw, int mov_pitch,
                float* flow, int ny, int nx, int ts, int r, void* stream);
 int hhsr_bm_l1(const float* ref, int ref_pitch, const float* mov, int mh, int mw, int mov_pitch,
                float* flow, int ny, int nx, int ts, int r, int mode, void* stream);
 
 /* ---- ICA (ICA.py:78-482): n_iter Gauss-Newton steps per tile, in place on `flow`.
- * flags bit 0: reproduce the ts=64 row off-by-one of ica_kernel_64 (ICA.py:437-449). */
+ * flags bit 0: reproduce the ts=64 row off-by-one of ica_kernel_64 (ICA.py:437-449).
+ * ref, gx and gy share ONE layout, ref_pitch (>= nx * ts): pass gx / gy as hhsr_grad_hessian wrote them for `ref` at that
+ * pitch; mov_pitch >= mw. */
 int hhsr_ica(const float* ref, const float* gx, const float* gy, int ref_pitch, const float* hess,
              const float* mov, int mh, int mw, int mov_pitch,
              float* flow, int ny, int nx, int ts, int n_iter, int flags, void* stream);
@@ -132,14 +146,16 @@ int hhsr_ica(const float* ref, const float* gx, const float* gy, int ref_pitch, 
  * Same results as hhsr_bm_* followed by hhsr_ica (flags bit 0 is irrelevant below ts = 64).
  * Incoming flow: `flow` itself (coarse_flow NULL, rep >= 0); or the nearest-neighbour upscaling of the coarser
  * level fused in (alignment.py:150-172): mult * coarse_flow[ty/rep][tx/rep] ([cny][cnx][2], zero past it); or
- * zero (coarse_flow NULL, rep < 0: the coarsest level).  `flow` is always the output. */
+ * zero (coarse_flow NULL, rep < 0: the coarsest level).  `flow` is always the output.
+ * ref_pitch >= rw, mov_pitch >= mw (error -1 otherwise), independent of each other; hess and the flows are compact. */
 int hhsr_align_level(const float* ref, int rh, int rw, int ref_pitch, const float* hess,
                      const float* mov, int mh, int mw, int mov_pitch,
                      float* flow, int ny, int nx, int ts, int r, int metric, int n_iter,
                      const float* coarse_flow, int cny, int cnx, int rep, float mult, void* stream);
 /* The same level step for n_frames moving frames against ONE reference level in one launch (HOST arrays of device
  * pointers; coarse_flows NULL or one pointer per frame): the coarse levels are 7-27 us launches of a few hundred
- * workgroups each — a chunk of frames fills the GPU where one frame cannot.  Per frame bit-identical. */
+ * workgroups each — a chunk of frames fills the GPU where one frame cannot.  Per frame bit-identical.  One mov_pitch for
+ * all moving levels. */
 int hhsr_align_level_batch(const float* ref, int rh, int rw, int ref_pitch, const float* hess,
                            const float* const* movs, int n_frames, int mh, int mw, int mov_pitch,
                            float* const* flows, int ny, int nx, int ts, int r, int metric, int n_iter,
@@ -152,7 +168,11 @@ int hhsr_flow_upscale_nearest(const float* src, int sny, int snx, float* dst, in
 
 /* ---- kernel covariances, Alg. 5 (kernels.py:29-243; utils_image.py:117-170, 346-357;
  * linalg.py:87-185), bayer mode: GAT -> 2x2 mean -> gradients -> structure tensor -> eigen ->
- * (k1, k2) -> covariance per Bayer quad.  law: 0 = hard_threshold, 1 = linear. */
+ * (k1, k2) -> covariance per Bayer quad.  law: 0 = hard_threshold, 1 = linear.
+ * The four Bayer passes over a raw frame (hhsr_cov_from_raw, hhsr_rob_stats, hhsr_frame_stats, hhsr_frame_stats_batch) load
+ * the (even, odd) pixel pair of a quad row at once: `pitch` must be EVEN and `raw` 8-byte aligned — a window of a larger
+ * frame starts at an even column — and covs 16-byte aligned (error -1 otherwise).  An odd last row / column belongs to no
+ * quad and is not read.  means / vars / covs are compact. */
 int hhsr_cov_from_raw(const float* raw, int H, int W, int pitch, float* covs,
                       double alpha, double beta, double k_detail, double k_denoise,
                       double D_th, double D_tr, double k_stretch, double k_shrink, int law,
@@ -170,7 +190,8 @@ int hhsr_frame_stats(const float* raw, int H, int W, int pitch, const uint8_t cf
                      double k_denoise, double D_th, double D_tr, double k_stretch, double k_shrink, int law,
                      void* stream);
 /* The same pass for n_frames comp frames (guide means + covariances, no variances) in one launch: HOST arrays of
- * device pointers; per frame bit-identical to hhsr_frame_stats. */
+ * device pointers; one (even) pitch for all frames, every raws[n] 8-byte aligned; per frame bit-identical to
+ * hhsr_frame_stats. */
 int hhsr_frame_stats_batch(const float* const* raws, int n_frames, int H, int W, int pitch, const uint8_t cfa[4],
                            const double* wb, float* const* means, float* const* covs, double alpha, double beta,
                            double k_detail, double k_denoise, double D_th, double D_tr, double k_stretch,
@@ -236,7 +257,8 @@ int hhsr_rob_sum(const float* const* rs, int n_frames, int H, int W, int flags, 
  * 145-148, 337-343; merge.py:131-137, 191-194, 349-354, 410): the frame is its own grey image (alignment unchanged), its
  * own one-channel guide image (no white balance) and the kernel covariances are estimated per pixel.
  * hhsr_mono_frame_stats: 3x3 local mean / variance [H][W] and / or covariances [H][W][2][2] in one pass
- *   (means NULL: covariances only; covs NULL: statistics only; vars may be NULL).
+ *   (means NULL: covariances only; covs NULL: statistics only; vars may be NULL); any pitch >= W, raw 4-byte aligned,
+ *   covs 16-byte aligned; the outputs are compact.
  * hhsr_mono_rob_upscale: robustness.py:296-421 on a one-channel map, which keeps its size while the kernel keeps its
  *   hard-coded s = 2 — the top-left quadrant stretched over the frame (+inf outside), reproduced as it is;
  *   flow NULL = the reference frame.
@@ -281,7 +303,8 @@ int hhsr_mono_rob_frame(const float* comp_means, int H, int W, const float* ref_
 /* ---- merge, Alg. 4 / Alg. 11 (merge.py; utils.py:62-120) --------------------------------------
  * hhsr_accumulate: one comp frame, num/den += (merge.py:291-434).
  * hhsr_accumulate_ref: the reference frame (merge.py:83-233); acc_rob = NULL disables the
- * accumulated-robustness widening (rad_max / max_multiplier / max_frame_count ignored). */
+ * accumulated-robustness widening (rad_max / max_multiplier / max_frame_count ignored).
+ * `pitch` (>= W, odd allowed, raw 4-byte aligned) is the raw frame's alone: flow, covs, r, acc_rob, num and den are compact. */
 int hhsr_accumulate(const float* raw, int H, int W, int pitch, const float* flow, int ny, int nx, int ts,
                     const float* covs, const float* r, const uint8_t cfa[4], double scale, int kflags,
                     float* num, float* den, int sH, int sW, void* stream);
@@ -303,6 +326,9 @@ int hhsr_add(float* A, const float* B, int64_t n, void* stream);          /* A +
  * keeps idx / scale in float32) and therefore the results do not depend on how the frame was split.
  * acc_r (optional, float32 [H][W], integer scales only) receives sum_n r_n — the accumulated robustness of
  * super_resolution.py:158-159 — at no extra HBM traffic (+= with HHSR_MERGE_LOAD_ACC).
+ * ONE `pitch` (>= W, odd allowed, 4-byte aligned bases) for all comp frames raws[] AND ref_raw; flows, covs, rs, ref_covs,
+ * acc_r, num and den are compact.  For a sub-image, raws[n] / ref_raw point at the sub-image's first row inside the
+ * full frame (pitch unchanged) and the other arrays at their matching rows.
  * Kernel choice (float32 weights): scale 2 and scale 3 with a BAYER cfa (red and blue on one diagonal, green on the other),
  * ts % 16 == 0 and even / exact output sizes run the wave-per-parity-class kernels (three channel accumulators per
  * sub-pixel; scale 3: frames whose window leaves the image are evaluated by the same code with border masks); other
@@ -350,8 +376,10 @@ int hhsr_merge_burst_chain(const float* const* raws, const float* const* flows, 
 /* ---- burst front end (utils_dng.py:149-160) ------------------------------------------------
  * Sensor counts uint16 [n_frames][H][pitch] -> normalised, white-balanced float32 [n_frames][H][W]:
  * v = (float32(count) - black[c]) / (white - black[c]); v *= wb[c] / wb[1], c = cfa[(y&1)*2 + (x&1)], in the
- * reference's float32 arithmetic (bit-identical to its NumPy expression).  black_levels / white_balance: HOST
- * double[3] indexed by colour (R, G, B); raw and out 16-byte aligned. */
+ * reference's float32 arithmetic (bit-identical to its NumPy expression, whatever the pitch: with W and pitch both
+ * multiples of 8 a thread converts 8 counts with one 16-byte load, otherwise count by count — the same operations).
+ * black_levels / white_balance: HOST double[3] indexed by colour (R, G, B); raw and out 16-byte aligned (error -1
+ * otherwise); frame n starts at raw + n * H * pitch; out is compact. */
 int hhsr_normalize_raw_u16(const uint16_t* raw, int n_frames, int H, int W, int pitch, const uint8_t cfa[4],
                            const double* black_levels, double white_level, const double* white_balance,
                            float* out, void* stream);

@@ -46,6 +46,130 @@ def test_argument_errors_do_not_touch_the_gpu():
     assert rc == -1
 
 
+def pitched_prototypes():
+    """{entry point: [names of its parameters that end in `pitch`]} from include/hhsr.h."""
+    src = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
+    out = {}
+    for name, params in re.findall(r"\bint\s+(hhsr_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", src, flags=re.S):
+        pitches = [w for w in re.findall(r"(\w+)\s*(?:,|$)", params.replace("\n", " ")) if w.endswith("pitch")]
+        if pitches:
+            out[name] = pitches
+    return out
+
+
+def test_every_pitched_entry_point_is_in_the_pitched_buffer_tests():
+    """A new entry point with a `pitch` parameter cannot arrive without a case in tests/test_pitched_buffers.py."""
+    protos = pitched_prototypes()
+    assert len(protos) >= 19 and protos["hhsr_align_level_batch"] == ["ref_pitch", "mov_pitch"], protos
+    src = open(os.path.join(ROOT, "tests", "test_pitched_buffers.py")).read()
+    missing = [n for n in protos if not re.search(r"\b%s\b" % n, src)]
+    assert not missing, f"pitched entry points without a test in tests/test_pitched_buffers.py: {missing}"
+
+
+class _Mem:
+    """Pointers for the argument-check calls.  With a device: offsets into one zeroed 64 MiB device tensor, far larger than
+    anything the calls below would read or write if a check were missing (frames of at most 64 x 96).  Without a device
+    nothing can launch, so the same offsets from an arbitrary aligned address do."""
+
+    def __init__(self):
+        import torch
+
+        self.t = torch.zeros(1 << 24, dtype=torch.float32, device="cuda") if torch.cuda.is_available() else None
+        self.base = self.t.data_ptr() if self.t is not None else 1 << 32
+        assert self.base % 256 == 0
+
+    def __call__(self, k, off=0):
+        """Slot k (1 MiB apart, 256-byte aligned) plus `off` bytes."""
+        return ctypes.c_void_p(self.base + (k << 20) + off)
+
+    def table(self, n, k0, off=0):
+        return (ctypes.c_void_p * n)(*[self.base + ((k0 + i) << 20) + off for i in range(n)])
+
+
+def test_pitch_and_alignment_arguments_are_refused():
+    """Every entry point with a pitch refuses pitch < width (-1, "invalid argument") before any HIP call; the Bayer
+    statistics refuse an odd pitch and a raw pointer that is not 8-byte aligned, hhsr_normalize_raw_u16 a raw / out that is
+    not 16-byte aligned.  Every other argument of each call is valid, and each call is first made with valid pitches too,
+    where it must NOT return -1 (so that a -1 below is the pitch's)."""
+    from handheld_super_resolution import _lib
+
+    lib = _lib.load()
+    m = _Mem()
+    H, W, ts = 64, 96, 16
+    ny, nx = H // ts, W // ts
+    cfa, wb = _lib.cfa_bytes([[0, 1], [1, 2]]), _lib.doubles([1.9, 1.0, 1.6])
+    taps = _lib.floats([1.0 / 9] * 9)
+    cov = (1e-3, 1e-5, 0.3, 3.0, 0.7, 1.0, 4.0, 2.0, 1)
+    bl = _lib.doubles([63, 64, 66])
+    st = None  # null stream
+
+    def tab(k0, n=3, off=0):
+        return m.table(n, k0, off)
+
+    # name -> f(pitch_a, pitch_b, raw_off, out_off): the call with everything else valid
+    calls = {
+        "hhsr_pad_circular": lambda a, b, ro, oo: lib.hhsr_pad_circular(m(0), H, W, a, m(1), H + 8, W + 8, b + 8, st),
+        "hhsr_gauss_decimate": lambda a, b, ro, oo: lib.hhsr_gauss_decimate(m(0), H, W, a, m(1), (b - 8) // 2, 2, taps, 9, st),
+        "hhsr_gauss_decimate_batch": lambda a, b, ro, oo: lib.hhsr_gauss_decimate_batch(
+            tab(0), 3, H, W, a, tab(4), (b - 8) // 2, 2, taps, 9, st),
+        "hhsr_grad_hessian": lambda a, b, ro, oo: lib.hhsr_grad_hessian(m(0), H, W, a, ts, m(1), m(2), m(3), st),
+        "hhsr_bm_l2": lambda a, b, ro, oo: lib.hhsr_bm_l2(m(0), a, m(1), H - 3, W - 5, b - 5, m(2), ny, nx, ts, 2, st),
+        "hhsr_bm_l1": lambda a, b, ro, oo: lib.hhsr_bm_l1(m(0), a, m(1), H - 3, W - 5, b - 5, m(2), ny, nx, ts, 2, 0, st),
+        "hhsr_ica": lambda a, b, ro, oo: lib.hhsr_ica(m(0), m(1), m(2), a, m(3), m(4), H - 3, W - 5, b - 5, m(5), ny, nx, ts,
+                                                      3, 0, st),
+        "hhsr_align_level": lambda a, b, ro, oo: lib.hhsr_align_level(
+            m(0), H, W, a, m(3), m(4), H - 3, W - 5, b - 5, m(5), ny, nx, ts, 2, 0, 3, None, 0, 0, 0, 1.0, st),
+        "hhsr_align_level_batch": lambda a, b, ro, oo: lib.hhsr_align_level_batch(
+            m(0), H, W, a, m(3), tab(4), 3, H - 3, W - 5, b - 5, tab(8), ny, nx, ts, 2, 0, 3, None, 0, 0, 0, 1.0, st),
+        "hhsr_cov_from_raw": lambda a, b, ro, oo: lib.hhsr_cov_from_raw(m(0, ro), H, W, a, m(1), *cov, st),
+        "hhsr_rob_stats": lambda a, b, ro, oo: lib.hhsr_rob_stats(m(0, ro), H, W, a, cfa, wb, m(1), m(2), st),
+        "hhsr_frame_stats": lambda a, b, ro, oo: lib.hhsr_frame_stats(m(0, ro), H, W, a, cfa, wb, m(1), m(2), m(3), *cov, st),
+        "hhsr_frame_stats_batch": lambda a, b, ro, oo: lib.hhsr_frame_stats_batch(
+            tab(0, off=ro), 3, H, W, a, cfa, wb, tab(4), tab(8), *cov, st),
+        "hhsr_mono_frame_stats": lambda a, b, ro, oo: lib.hhsr_mono_frame_stats(m(0), H, W, a, m(1), m(2), m(3), *cov, st),
+        "hhsr_accumulate": lambda a, b, ro, oo: lib.hhsr_accumulate(
+            m(0), H, W, a, m(1), ny, nx, ts, m(2), m(3), cfa, 2.0, 0, m(4), m(6), 2 * H, 2 * W, st),
+        "hhsr_accumulate_ref": lambda a, b, ro, oo: lib.hhsr_accumulate_ref(
+            m(0), H, W, a, m(2), cfa, 2.0, 0, None, 0, 0.0, 0.0, m(4), m(6), 2 * H, 2 * W, st),
+        "hhsr_merge_burst": lambda a, b, ro, oo: lib.hhsr_merge_burst(
+            tab(0), tab(3), tab(6), tab(9), 3, H, W, a, ny, nx, ts, m(12), m(13), cfa, 2.0, 0, 2 | 4, m(14), None, None,
+            2 * H, 2 * W, 0, 2 * H, 0, st),
+        "hhsr_merge_burst_chain": lambda a, b, ro, oo: lib.hhsr_merge_burst_chain(
+            tab(0), tab(3), tab(6), tab(9), 3, H, W, a, ny, nx, ts, None, None, cfa, 2.0, 0, 32, m(14), None, None,
+            2 * H, 2 * W, m(15), 0, st),
+        "hhsr_normalize_raw_u16": lambda a, b, ro, oo: lib.hhsr_normalize_raw_u16(
+            m(0, ro), 3, H, W, a, cfa, bl, 16383.0, wb, m(4, oo), st),
+    }
+    protos = pitched_prototypes()
+    assert sorted(calls) == sorted(protos), sorted(set(protos) ^ set(calls))
+
+    missed = []  # every missing check is reported, not only the first
+
+    def refused(name, *args):
+        rc = calls[name](*args)
+        if not (rc == -1 and b"invalid argument" in lib.hhsr_last_error()):
+            missed.append((name, args, rc, lib.hhsr_last_error()))
+
+    for name, pitches in protos.items():
+        rc = calls[name](W, W, 0, 0)  # valid: launches on a device, fails in the HIP runtime without one, but never -1
+        assert rc >= 0, (name, rc, lib.hhsr_last_error())
+        refused(name, W - 1, W, 0, 0)
+        if len(pitches) == 2:  # dst_pitch < Wp / w2, mov_pitch < mw
+            refused(name, W, W - 1, 0, 0)
+    for name in ("hhsr_cov_from_raw", "hhsr_rob_stats", "hhsr_frame_stats", "hhsr_frame_stats_batch"):
+        refused(name, W + 1, W, 0, 0)   # the kernel loads (even, odd) pixel pairs: rows must stay 8-byte aligned
+        refused(name, W + 2, W, 4, 0)   # a raw pointer that is 4-byte but not 8-byte aligned
+        assert calls[name](W + 2, W, 8, 0) >= 0
+    refused("hhsr_normalize_raw_u16", W, W, 8, 0)
+    refused("hhsr_normalize_raw_u16", W, W, 0, 8)
+    assert calls["hhsr_normalize_raw_u16"](W + 2, W, 16, 16) >= 0
+    if m.t is not None:
+        import torch
+
+        torch.cuda.synchronize()
+    assert not missed, missed
+
+
 def test_no_cpu_fallback():
     import numpy as np
     import torch

@@ -470,9 +470,10 @@ def test_robustness_kernels_vs_oracle(H, W, ts, kernel):
     """hhsr_rob_frame / hhsr_rob_frames choose k_rob_frame_row4 / k_rob_frames_row4 (ts % 16 == 0, W % 4 == 0),
     k_rob_frame_tile (ts % 16 == 0, W = 2 mod 4) and k_rob_frame (everything else); each against oracle.compute_robustness
     on a grid with nblk % 8 != 0 (32 x 32-pixel workgroups: 11 x 7 = 77; k_rob_frame's 64 x 4: 6 x 50 = 300).  k_rob_frame is
-    reached through ts = 8: the other routes to it (a noise curve of more than 1024 entries, planes that are not 16-byte
-    aligned) are not inputs the Python API accepts or produces (the curves have 1001 entries, torch allocations are
-    aligned)."""
+    reached through ts = 8.  A noise curve of more than 1024 entries is not an input the Python API accepts (the curves have
+    1001 entries); the other routes to it and to k_rob_frame_tile (no packed curve index, planes that are not 16-byte
+    aligned) are not inputs the Python API produces (torch allocations are aligned), but a C client produces them with one
+    pointer offset: tests/test_pitched_buffers.py::test_rob_frame_kernels_chosen_by_pointer reaches them through the C ABI."""
     cfg, cfa, wb, comp, flows, want, rm, rv, curves = _rob_case(H, W, ts, 40 + ts)
     assert (ts % 16 == 0) == (kernel != "k_rob_frame") and (W % 4 == 0) == (kernel == "k_rob_frames_row4")
     for k, (c, f) in enumerate(zip(comp, flows)):
