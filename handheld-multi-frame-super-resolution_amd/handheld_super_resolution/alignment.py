@@ -6,6 +6,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
+from .config import hip_opt
 from .ICA import init_ica, align_lvl_ica
 from .block_matching import align_lvl_block_matching_L2, align_lvl_block_matching_L1
 from .utils_image import cuda_downsample, cuda_downsample_batch
@@ -87,8 +88,7 @@ def _fused_level(l, config):
     """(metric code, ts, r) when level l runs on the fused block-matching + ICA kernel, else None."""
     bm = config.block_matching.tuning
     ts, r = bm.tile_sizes[l], bm.search_radii[l]
-    hip = config.get("hip", None) if hasattr(config, "get") else None
-    fused = True if hip is None else bool(hip.get("fused_align", True))
+    fused = bool(hip_opt(config, "fused_align"))
     code = {"L2": 0, "L1": 1, "L1_ref_effective": 2}.get(bm.metrics[l])
     if fused and code is not None and ts in (8, 16, 32) and r in (1, 2, 4) and not (code != 0 and ts == 8):
         return code, ts, r

@@ -17,7 +17,7 @@ from __future__ import annotations
 import copy
 from typing import Any, Mapping
 
-__all__ = ["Config", "OmegaConf", "DEFAULTS", "default_config"]
+__all__ = ["Config", "OmegaConf", "DEFAULTS", "default_config", "HIP_KNOBS", "hip_opt"]
 
 
 class Config(dict):
@@ -230,3 +230,35 @@ def default_config(**overrides) -> Config:
     if overrides:
         _merge_into(cfg, overrides)
     return cfg
+
+
+# The switches of this build, `config.hip` (not in the reference schema; all optional, unknown keys are ignored): name ->
+# default.  None: the default depends on the burst and is derived by the one place that reads the knob.
+HIP_KNOBS = {
+    "graph": True,             # HIP-graph replay of repeated bursts (graph.py)
+    "batch": True,             # one launch per stage and CHUNK of frames instead of per frame
+    "fused_merge": True,       # the whole burst in one merge launch; false: the sequential operator path
+    "fused_align": True,       # block matching + ICA of a level in one kernel
+    "weight_fp64": False,      # the reference's float64 weight chain in the merge
+    "merge_kernel": "auto",    # auto | generic | tile | x2_v1 (validation)
+    "strategy": "rows",        # multi-GPU: rows | reduce
+    "stage_frames": 0,         # multi-GPU "rows": frames per stage, 0 = one stage (measured: distributed.main_sharded)
+    "chunk": None,             # frames per chunk: super_resolution.ROB_GROUP
+    "streams": None,           # side streams: super_resolution.DEFAULT_STREAMS, 1 from LARGE_FRAME pixels
+    "merge_chain": None,       # host-resident bursts, chained merge: on for frames of 4-byte items
+    "merge_link_after": None,  # ... explicit chunk indices after which a link runs (tuning)
+    "host_chunk_sizes": None,  # ... explicit chunk sizes (tuning)
+    "inject_flows": None,      # per-frame flow fields that replace the alignment (validation)
+    "raw_norm": None,          # {"black_levels", "white_level"} of frames given as integer sensor counts
+    "max_flow": None,          # multi-GPU "rows": bound on |flow_y|; measured when absent
+    "align_cost": None,        # multi-GPU "rows": distributed.align_cost(scale)
+}
+
+
+def hip_opt(config, name):
+    """config.hip[name], or the default of HIP_KNOBS.  Read at call time: configurations are edited in place.  `config`
+    may lack `.get` or `hip`; `hip` is any mapping (Config, dict, DictConfig).  A name that is not a knob is a KeyError."""
+    default = HIP_KNOBS[name]
+    hip = config.get("hip", None) if hasattr(config, "get") else None
+    return default if hip is None else hip.get(name, default)
+

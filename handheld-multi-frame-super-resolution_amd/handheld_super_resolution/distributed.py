@@ -13,7 +13,7 @@ One process per GPU, two selectable strategies (`main_sharded(..., strategy=)`, 
   rounds (round r = frames r G .. r G + G - 1, one per rank: stage_plan) and stage s's flows are gathered and its frames'
   step B (raw pass, robustness on the slab) runs while stage s + 1 is being aligned — step A on one HIP stream, step B
   on another, the RCCL all-gather between them, every piece a HIP graph on replay (RowsPlan).  Measured per-rank
-  compute says ONE stage is faster on this hardware (STAGE_FRAMES below), so that is the default: the same plan with a
+  compute says ONE stage is faster on this hardware (config.hip.stage_frames, main_sharded), so that is the default: the same plan with a
   single all-gather, and still no host read between step A and step B.  The sub-image extent
   needs a bound on |flow_y| BEFORE the flows exist: the plan is captured with the bound its first (eager) burst measured
   plus a margin, every burst checks its gathered flows against it on the device, the host reads that flag when the last
@@ -54,6 +54,9 @@ import math
 import torch
 import torch.distributed as dist
 
+from .config import hip_opt
+from .merge import merge, merge_burst, merge_fusions, merge_ref, scale_is_pow2
+
 SLAB_ALIGN = 96  # slabs start on the workgroup grids of all merge kernels: 32 output rows (x2), 48 (x3), 16 (tile kernel)
 HALO = 12        # rows of context beyond slab + |flow|.  r[y] = min of R over y +- 2 (robustness.py:641-686); R[y'] reads
                  # the guide statistics at (y' + flow) / 2 with Dodgson taps +- 1.5 guide pixels on 3 x 3 local means
@@ -82,12 +85,6 @@ def slab_rows(sH, world):
     return -(-rows // SLAB_ALIGN) * SLAB_ALIGN
 
 
-STAGE_FRAMES = 0  # frames per stage of strategy "rows" (config.hip.stage_frames); 0 = ONE stage: step A of all the rank's
-                  # frames in one batched launch per kernel, one all-gather, step B.  Measured (tools/debug/emulate_ranks.py, one
-                  # MI355X running each rank's graphs, 12 MP x 20 x2, per-rank compute at G = 8): one stage 1.85 ms, stages of
-                  # >= 4 frames (3 stages) 2.22 ms — the step-A kernels of ONE frame per launch are latency-bound (they were
-                  # sized for chunks of 4), and step A and step B on two streams do not overlap: either fills the GPU
-                  # (G = 1: 9.81 ms pipelined, 3.81 + 5.84 alone).  Staging pays only where the all-gather's latency does.
 def align_cost(scale):
     """rho: step A of one frame costs about as much as step B of one frame over this fraction of the image.  Step A does
     not depend on the scale, step B grows with the output: B / A = 0.20 + 0.32 scale^2 fits the per-rank measurements of
@@ -96,9 +93,6 @@ def align_cost(scale):
     0.68 ms at 48 MP; B 0.276 / 2.2 ms per frame and image): B / A = 0.74 + 0.276 scale^2, rho 0.54 at x2 and 0.31 at x3.
     config.hip.align_cost overrides it."""
     return 1.0 / (0.74 + 0.276 * float(scale) ** 2)
-
-
-ALIGN_COST = align_cost(2)  # (the x2 value; main_sharded uses align_cost(config.scale))
 
 
 def slab_bounds(sH, world, n_frames=0, align_cost=0.0, align=SLAB_ALIGN):
@@ -170,11 +164,10 @@ class HipEngine:
     """Per-rank compute on the local MI355X."""
 
     def __init__(self, config):
-        from .super_resolution import denoiser_enabled
+        from .super_resolution import accumulation
 
         self.config = config
-        self.denoiser_on = denoiser_enabled(config)
-        self.accumulate_r = self.denoiser_on or bool(config.robustness.save_mask)
+        self.denoiser_on, self.accumulate_r = accumulation(config)
         self.pipe = None
         self._runner = None  # HIP-graph replay of main() for device-resident bursts (graph.py)
         self._plans, self._plan_seen, self._bounds = {}, {}, {}  # strategy "rows": RowsPlan per input set, measured flow bounds
@@ -187,9 +180,7 @@ class HipEngine:
         when the same device tensors come back (config.hip.graph, default on; the first call runs eagerly, the second
         captures): the returned tensors then belong to the graph and are overwritten by the next call."""
         from .super_resolution import main
-        from .graph import GraphRunner, capturable
-
-        from .graph import HostBurstRunner
+        from .graph import GraphRunner, HostBurstRunner, capturable
 
         if HostBurstRunner.usable(self.config, ref_img, comp_imgs):
             # host-resident burst: eager uploads + per-chunk HIP graphs over static staging buffers (graph.py); the
@@ -359,7 +350,6 @@ class HipEngine:
 
         def fn(ref, *frames):
             from .super_resolution import BurstPipeline
-            from .merge import merge_burst, can_fuse_acc_r
 
             cfg = self.config
             self.pipe = pipe = BurstPipeline(cfg).init_ref(ref)
@@ -372,8 +362,7 @@ class HipEngine:
             acc_r = (torch.zeros((H, W), dtype=torch.float64 if self.denoiser_on else torch.float32, device=self.device)
                      if self.accumulate_r else None)
             if frames:
-                fuse_acc = acc_r is not None and not self.denoiser_on and can_fuse_acc_r(cfg)
-                fuse_min = pipe.fuses_local_min() and (fuse_acc or acc_r is None)
+                fuse_acc, fuse_min = merge_fusions(cfg, (H, W), len(frames), self.accumulate_r, self.denoiser_on)
                 fr = pipe.process_frames(list(frames), None if (fuse_acc or self.denoiser_on) else acc_r, fuse_local_min=fuse_min)
                 if self.denoiser_on:
                     for f in fr:
@@ -402,7 +391,6 @@ class HipEngine:
         accumulated-robustness denoiser (merge.py:223-228) `acc_r` is the REDUCED robustness [H, W] and the reference
         frame goes through the sequential operator on the sub-image of the slab (like SlabWork)."""
         from .graph import GraphRunner, capturable
-        from .merge import merge_burst, merge_ref
         from .utils import divide
 
         cfg = self.config
@@ -413,8 +401,7 @@ class HipEngine:
         def fn(acc, ref, covs, *rob):
             if self.denoiser_on:
                 scale, ts = cfg.scale, self.tile_size()
-                pow2 = float(scale) in (1.0, 2.0, 4.0, 8.0)
-                S0, S1, row0 = sub_image_rows(r0, r1, scale, H, ts, 0.0, from_top=not pow2)
+                S0, S1, row0 = sub_image_rows(r0, r1, scale, H, ts, 0.0, from_top=not scale_is_pow2(scale))
                 q = 1 if self.pipe.mono else 2  # covariances: one per Bayer quad (monochrome: per pixel)
                 num = torch.zeros((int(round(scale * (S1 - S0))), acc.shape[2], 3), dtype=torch.float32, device=acc.device)
                 den = torch.zeros_like(num)
@@ -450,7 +437,6 @@ class SlabWork:
 
     def __init__(self, eng, ref_dev, r0, r1, max_flow_y, ny_full, ref_wait=True):
         from .super_resolution import BurstPipeline
-        from .merge import can_fuse_acc_r
         from .robustness import RobustnessSum
 
         cfg = self.cfg = eng.config
@@ -458,10 +444,9 @@ class SlabWork:
         H, W = ref_dev.shape
         scale, ts = cfg.scale, eng.tile_size()
         sW = round(scale * W)
-        pow2 = float(scale) in (1.0, 2.0, 4.0, 8.0)
         # (the per-frame operator path of the denoiser has no row offset: for scales whose positions idx / scale are
         # not exact in float32 its sub-image starts at the top of the frame, where sub-image = full-frame coordinates)
-        S0, S1, row0 = sub_image_rows(r0, r1, scale, H, ts, max_flow_y, from_top=eng.denoiser_on and not pow2)
+        S0, S1, row0 = sub_image_rows(r0, r1, scale, H, ts, max_flow_y, from_top=eng.denoiser_on and not scale_is_pow2(scale))
         self.S0, self.S1, self.row0, self.nrows = S0, S1, row0, r1 - r0
         Hs = S1 - S0
         self.sHs = int(round(scale * Hs))
@@ -485,14 +470,12 @@ class SlabWork:
             # merged: sequential operator path on the sub-image
             self.num = torch.zeros((self.sHs, sW, 3), dtype=torch.float32, device=dev)
             self.den = torch.zeros_like(self.num)
-        else:
-            self.fuse_acc = self.acc_r is not None and can_fuse_acc_r(cfg)
-            self.fuse_min = sub.fuses_local_min() and (self.fuse_acc or self.acc_r is None) and row0 % slab_align(scale) == 0
+        # (frames arrive in front(): the rule is asked for "some"; finish() copes with a slab that got none)
+        self.fuse_acc, fuse_min = merge_fusions(cfg, (Hs, W), 1, eng.accumulate_r, eng.denoiser_on)
+        self.fuse_min = fuse_min and row0 % slab_align(scale) == 0
 
     def front(self, imgs, flows):
         """`imgs`: full frames (their rows [S0, S1) are used); `flows`: their FULL flow fields [ny, nx, 2] (views welcome)."""
-        from .merge import merge
-
         sub, S0, S1 = self.sub, self.S0, self.S1
         sub_flows = [f[self.t0:self.t1] for f in flows]
         if self.eng.denoiser_on:
@@ -505,7 +488,6 @@ class SlabWork:
                                               fuse_local_min=self.fuse_min, flows=sub_flows)
 
     def finish(self):
-        from .merge import merge_ref, merge_burst
         from .utils import divide
 
         sub, cfg = self.sub, self.cfg
@@ -744,14 +726,6 @@ def _staged(t, group):
     return t.is_cuda and dist.get_backend(group) != "nccl"
 
 
-def _all_gather(t, world, group):
-    """Equal-size all-gather: [world, *t.shape].  RCCL ("nccl") gathers device tensors in place over xGMI."""
-    src = t.cpu() if _staged(t, group) else t.contiguous()
-    out = torch.empty((world, *src.shape), dtype=src.dtype, device=src.device)
-    dist.all_gather_into_tensor(out, src, group=group) if src.is_cuda else dist.all_gather(list(out.unbind(0)), src, group=group)
-    return out.to(t.device)
-
-
 def _all_gather_stage(out, src, world, group, streams=None):
     """out [world, *src.shape] <- every rank's src (one stage's flow fields).  `streams` = (producer, consumer) HIP
     streams of a RowsPlan: RCCL reads `src` once the producer stream has written it and only the CONSUMER stream waits
@@ -836,8 +810,7 @@ def _all_reduce(t, group):
 
 def _strategy(config, strategy):
     if strategy is None:
-        hip = config.get("hip", None) if hasattr(config, "get") else None
-        strategy = hip.get("strategy", "rows") if hip is not None else "rows"
+        strategy = hip_opt(config, "strategy")
     if strategy not in ("rows", "reduce"):
         raise ValueError(f"unknown multi-GPU strategy {strategy!r} (rows | reduce)")
     return strategy
@@ -906,13 +879,17 @@ def main_sharded(ref_img, comp_imgs, config, group=None, engine=None, gather=Tru
         # normalisation of the slab (HipEngine on device-resident bursts: RowsPlan, pipelined over two streams)
         H, W = tuple(ref_img.shape)
         sH, sW = round(config.scale * H), round(config.scale * W)
-        hip = config.get("hip", None) if hasattr(config, "get") else None
-        if max_flow is None and hip is not None:
-            max_flow = hip.get("max_flow", None)
-        cost = align_cost(config.scale)
-        if hip is not None and hip.get("align_cost", None) is not None:
-            cost = float(hip.get("align_cost"))
-        sf = int(hip.get("stage_frames", STAGE_FRAMES)) if hip is not None else STAGE_FRAMES
+        if max_flow is None:
+            max_flow = hip_opt(config, "max_flow")
+        cost = hip_opt(config, "align_cost")
+        cost = align_cost(config.scale) if cost is None else float(cost)
+        # frames per stage; 0 = ONE stage: step A of all the rank's frames in one batched launch per kernel, one all-gather,
+        # step B.  Measured (tools/debug/emulate_ranks.py, one MI355X running each rank's graphs, 12 MP x 20 x2, per-rank
+        # compute at G = 8): one stage 1.85 ms, stages of >= 4 frames (3 stages) 2.22 ms — the step-A kernels of ONE frame
+        # per launch are latency-bound (they were sized for chunks of 4), and step A and step B on two streams do not overlap:
+        # either fills the GPU (G = 1: 9.81 ms pipelined, 3.81 + 5.84 alone).  Staging pays only where the all-gather's
+        # latency does.
+        sf = int(hip_opt(config, "stage_frames"))
         stages = stage_plan(n, world, sf if sf > 0 else max(n, 1))
         bounds = slab_bounds(sH, world, n, cost, slab_align(config.scale))
         rows = max(b1 - b0 for b0, b1 in zip(bounds[:-1], bounds[1:]))  # (padded chunk of the optional gather)

@@ -19,6 +19,9 @@ import threading
 
 import torch
 
+from .config import Config, hip_opt
+from .merge import can_chain, chain_buffer, merge_burst, merge_burst_chain, merge_fusions
+
 
 _shared = {}  # device index -> (main stream, high-priority upload stream) shared by every runner of the process
 
@@ -190,8 +193,6 @@ class HostBurstRunner:
         # blocked for 8.7 ms; with the upload stream in the high-priority queue set: none).  Both streams are shared by
         # all runners of the process (shared_streams).
         self.main, self.up = shared_streams(device)
-        import threading
-
         self._lock = threading.Lock()  # one burst at a time per runner (static staging, shared streams)
 
     def _eager(self, ref_img, comp_imgs):
@@ -231,14 +232,10 @@ class HostBurstRunner:
         denoiser: those keep the eager path)."""
         import numpy as np
 
-        hip = config.get("hip", None) if hasattr(config, "get") else None
-        if hip is not None and (hip.get("inject_flows", None) is not None or not hip.get("graph", True)
-                                or not hip.get("fused_merge", True)):
-            return False
-        if config.verbose != 0 or config.debug or config.mode != "bayer":
-            return False
-        den = config.accumulated_robustness_denoiser
-        if bool(den.get("enabled", False)) or bool(den.median.enabled or den.gauss.enabled or den.merge.enabled):
+        from .super_resolution import denoiser_enabled
+
+        if not capturable(config, ()) or not hip_opt(config, "fused_merge") or config.mode != "bayer" \
+                or denoiser_enabled(config, store=False):
             return False
         frames = [ref_img, *[comp_imgs[i] for i in range(len(comp_imgs))]]
         if len(frames) < 2:
@@ -296,8 +293,7 @@ class HostBurstRunner:
 
     # ---- capture --------------------------------------------------------------------------------------------------
     def _capture(self, frames):
-        from .super_resolution import BurstPipeline, _Staged, _stream_pool, denoiser_enabled
-        from .merge import merge_burst, can_fuse_acc_r
+        from .super_resolution import BurstPipeline, _Staged, _stream_pool
 
         cfg, dev = self.config, self.device
         n = len(frames) - 1
@@ -317,8 +313,7 @@ class HostBurstRunner:
             with capture(st.g_ref, st.main):
                 pipe.init_ref(staged[0])
             sH, sW = pipe.output_size()
-            fuse_acc = accumulate_r and can_fuse_acc_r(cfg)
-            fuse_min = pipe.fuses_local_min() and (fuse_acc or not accumulate_r)
+            fuse_acc, fuse_min = merge_fusions(cfg, (H, W), n, accumulate_r, False)  # (usable(): never with the denoiser)
             acc_r = torch.zeros((H, W), dtype=torch.float32, device=dev) if accumulate_r else None
             if accumulate_r and not fuse_acc:
                 raise RuntimeError("accumulated robustness at a non-integer scale: eager path")
@@ -327,8 +322,7 @@ class HostBurstRunner:
             if len(pool) < ns:
                 pool += [torch.cuda.Stream(dev) for _ in range(ns - len(pool))]
             st.chunks = host_chunks(n, pipe._chunk_size())
-            hip_ = cfg.get("hip", None) if hasattr(cfg, "get") else None
-            sizes = None if hip_ is None else hip_.get("host_chunk_sizes", None)  # explicit chunk sizes (tuning)
+            sizes = hip_opt(cfg, "host_chunk_sizes")  # explicit chunk sizes (tuning)
             if sizes is not None:
                 from ._lib import MAX_BATCH
 
@@ -363,15 +357,13 @@ class HostBurstRunner:
             # only has the final single-frame chunks, the reference frame and the normalisation left (12 MP x 20: 1.4 ms
             # instead of 4.0 after the last frame's front end).  Each link moves the 1.6 GB of accumulators twice (~0.7 ms
             # of otherwise idle GPU time): not for GPU-bound bursts.
-            from .merge import can_chain, chain_buffer, merge_burst_chain
-
-            hip = cfg.get("hip", None) if hasattr(cfg, "get") else None
-            want_chain = (frames[0].dtype.itemsize >= 4) if hip is None or hip.get("merge_chain", None) is None \
-                else bool(hip.get("merge_chain"))
+            want_chain = hip_opt(cfg, "merge_chain")
+            if want_chain is None:
+                want_chain = frames[0].dtype.itemsize >= 4
             st.links = []  # (index of the chunk after which the link runs, frames merged once it has run)
             if want_chain and fuse_min and can_chain(cfg, (H, W)) and len(st.chunks) > 2:
                 done = 0
-                after = None if hip is None else hip.get("merge_link_after", None)  # explicit chunk indices (tuning)
+                after = hip_opt(cfg, "merge_link_after")  # explicit chunk indices (tuning)
                 for c, idx in enumerate(st.chunks[:-1]):
                     done = idx[-1] + 1
                     if (len(idx) >= 2) if after is None else (c in after):
@@ -506,8 +498,6 @@ def host_chunks(n, size):
     while rem > 0:
         body.append(min(size, rem))
         rem -= body[-1]
-    if len(body) > 1 and body[-1] < body[-2]:  # the remainder chunk goes first of the short ones: sizes never grow
-        pass
     sizes = body + tail[::-1]
     out, i = [], 0
     for k in sizes:
@@ -557,8 +547,6 @@ class ConfigWatch:
         self.config = None  # keeps the watched object alive: its id() cannot be reused
 
     def changed(self, config):
-        from .config import Config
-
         state = self._state(config) if isinstance(config, Config) else signature(config)
         first = self.state is None or self.config is not config
         same = state == self.state and not first
@@ -567,8 +555,6 @@ class ConfigWatch:
 
     @staticmethod
     def _state(config):
-        from .config import Config
-
         out, stack = [], [config]
         while stack:
             c = stack.pop()
@@ -586,8 +572,7 @@ class ConfigWatch:
 
 
 def capturable(config, tensors):
-    """main() can be captured: no host-synchronising timers / debug copies / injected host arrays, device inputs."""
-    hip = config.get("hip", None) if hasattr(config, "get") else None
-    if hip is not None and (hip.get("inject_flows", None) is not None or not hip.get("graph", True)):
-        return False
-    return config.verbose == 0 and not config.debug and all(torch.is_tensor(t) and t.is_cuda for t in tensors)
+    """main() can be captured: config.hip.graph on, no host-synchronising timers / debug copies / injected host arrays,
+    device inputs (no tensors: the verdict on the configuration alone, HostBurstRunner.usable)."""
+    return bool(hip_opt(config, "graph")) and hip_opt(config, "inject_flows") is None and config.verbose == 0 \
+        and not config.debug and all(torch.is_tensor(t) and t.is_cuda for t in tensors)

@@ -3,6 +3,7 @@
 import torch
 
 from . import _lib
+from .config import hip_opt
 
 
 # kflags of the C ABI (include/hhsr.h)
@@ -16,9 +17,8 @@ def _common(config):
     reference's Numba typing; default float32 weights with float64 geometry), bits 2-4 = restriction of
     hhsr_merge_burst's kernel choice (config.hip.merge_kernel: auto | generic | tile | x2_v1; validation only),
     bit 5 = `mode: grey` (one channel, per-pixel covariances)."""
-    hip = config.get("hip", None) if hasattr(config, "get") else None
-    f64 = bool(hip.get("weight_fp64", False)) if hip is not None else False
-    force = _FORCE[str(hip.get("merge_kernel", "auto"))] if hip is not None else 0
+    f64 = bool(hip_opt(config, "weight_fp64"))
+    force = _FORCE[str(hip_opt(config, "merge_kernel"))]
     return float(config.scale), ((KERNEL_ISO if config.merging.kernel == "iso" else 0) | (WEIGHT_F64 if f64 else 0) |
                                  force | (SENSOR_MONO if config.mode != "bayer" else 0))
 
@@ -76,6 +76,20 @@ def can_fuse_local_min(config, shape):
     if kflags & SENSOR_MONO:  # monochrome: the x2 tile kernel only
         return ok and scale == 2.0 and not (kflags & FORCE_X2V1)
     return ok and ((scale == 2.0 and H % 2 == 0 and W % 2 == 0) or (scale == 3.0 and W % 4 == 0 and _is_bayer(config)))
+
+
+def merge_fusions(config, shape, n_comp, accumulate_r, denoiser_on):
+    """(fuse_acc, fuse_min): the fused merge of `n_comp` frames of `shape` also sums the robustness maps / takes their 5x5
+    local minimum itself — the ONE rule of main(), the host-resident runner and both multi-GPU strategies.  The denoiser
+    decides on a float64 sum, not the merge's float32 one; a map accumulated apart from the merge needs the filtered maps."""
+    fuse_acc = bool(accumulate_r and not denoiser_on and n_comp > 0 and can_fuse_acc_r(config))
+    fuse_min = bool(config.robustness.enabled and can_fuse_local_min(config, shape) and (fuse_acc or not accumulate_r))
+    return fuse_acc, fuse_min
+
+
+def scale_is_pow2(scale):
+    """1, 2, 4, 8: (h + 0.5) / scale is exact in float32 — mirrors scale_is_pow2() of hhsr_merge.hip."""
+    return float(scale) in (1.0, 2.0, 4.0, 8.0)
 
 
 def merge_burst(frames, ref_img, ref_kernels, num, den, cfa_pattern, config, load_acc=False, do_ref=True,

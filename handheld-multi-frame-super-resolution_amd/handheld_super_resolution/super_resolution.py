@@ -14,13 +14,16 @@ MI355X design notes (vs the reference's per-frame Python loop):
   * multi-GPU (distributed.py): alignment frame-parallel, one all-gather of the flow fields, robustness / kernels /
     merge row-parallel (default), or frames one per GPU with one reduce-scatter of the num / den accumulators.
 """
+import atexit
 import os
+import threading
 import time
 
 import numpy as np
 import torch
 
 from . import _lib
+from .config import hip_opt
 from .utils_image import compute_grey_images, compute_grey_images_batch
 from .utils import divide, add, getTime, timer
 from .alignment import (align, init_alignment, build_gaussian_pyramid, build_gaussian_pyramids, align_batch,
@@ -29,21 +32,39 @@ from .params import sanitize_config, update_snr_config
 from .robustness import (init_robustness, compute_robustness, compute_robustness_group, noise_curves_to_device, RobustnessSum,
                          ref_planes, upscale_warp_stats, mono_sigma_sq)
 from .kernels import estimate_kernels, frame_stats, frame_stats_batch
-from .merge import merge, merge_ref, merge_burst, can_fuse_acc_r, can_fuse_local_min
+from .merge import merge, merge_ref, merge_burst, can_fuse_acc_r, merge_fusions
 
 
-def denoiser_enabled(config):
-    """config.accumulated_robustness_denoiser.enabled is derived by process() upstream
-    (super_resolution.py:291-296); derive it here too when main() is called directly."""
+def denoiser_enabled(config, store=True):
+    """config.accumulated_robustness_denoiser.enabled is derived by process() upstream (super_resolution.py:291-296);
+    derive it here too when main() is called directly (`store=False`: without writing it into the configuration)."""
     den = config.accumulated_robustness_denoiser
     if "enabled" in den:
         return bool(den.enabled)
-    den.enabled = bool(den.median.enabled or den.gauss.enabled or den.merge.enabled)
-    return den.enabled
+    on = bool(den.median.enabled or den.gauss.enabled or den.merge.enabled)
+    if store:
+        den.enabled = on
+    return on
 
 
-def n_images_of(comp_imgs):
-    return len(comp_imgs)
+def accumulation(config):
+    """(denoiser_on, accumulate_r): the accumulated robustness is needed by the denoiser or asked for as a mask."""
+    denoiser_on = denoiser_enabled(config)
+    return denoiser_on, denoiser_on or bool(config.robustness.save_mask)
+
+
+def main_plan(config, shape, n_comp, denoiser_on, accumulate_r):
+    """main()'s path for a burst: (fused, batch, fuse_acc, fuse_min, den_fused).  fused: ONE merge launch (not with the
+    denoiser); batch: the frames go through process_frames(), not the per-frame loop of the timers and debug copies;
+    den_fused: the denoiser's form of both — one merge launch without the reference frame, the float64 robustness sum in
+    one pass (it takes the 5x5 minimum on the way in: fuse_min whatever is accumulated), then merge_ref and divide."""
+    fused_merge = bool(hip_opt(config, "fused_merge"))
+    quiet = not (config.verbose >= 1 or bool(config.debug))
+    fused = fused_merge and not denoiser_on
+    den_fused = fused_merge and denoiser_on and can_fuse_acc_r(config) and n_comp > 0 and quiet
+    batch = (fused and quiet) or den_fused
+    fuse_acc, fuse_min = merge_fusions(config, shape, n_comp, accumulate_r and not den_fused, denoiser_on)
+    return fused, batch, fused and fuse_acc, batch and fuse_min, den_fused
 
 
 def _device():
@@ -105,11 +126,10 @@ class BurstPipeline:
         self.grey_method = config.grey_method
         self.ref = None
         self._streams = _stream_pool.setdefault(self.device.index, [])
-        hip = config.get("hip", None) if hasattr(config, "get") else None
         # validation hook (bench.py's parity attribution, tests): per-frame flow fields that replace align()
-        self._inject_flows = hip.get("inject_flows", None) if hip is not None else None
+        self._inject_flows = hip_opt(config, "inject_flows")
         # frames given as integer sensor counts: {"black_levels": [R, G, B], "white_level": w} (see _ingest)
-        self._raw_norm = hip.get("raw_norm", None) if hip is not None else None
+        self._raw_norm = hip_opt(config, "raw_norm")
         # chunk-batched front end (one launch per stage for a chunk of frames, see _front_chunk); config.hip.batch: false
         # keeps the per-frame launches (A/B, tests)
         # (before, after): the flow fields handed to this pipeline are row slices (views) of larger fields with that many
@@ -119,8 +139,7 @@ class BurstPipeline:
         # before the frames itself (distributed.RowsPlan captures them as separate graphs: an event recorded in one
         # capture cannot be waited for in another)
         self.ref_wait = True
-        self._batch = (True if hip is None else bool(hip.get("batch", True))) \
-            and (self.mono or self.grey_method == "FFT") and config.verbose < 2
+        self._batch = bool(hip_opt(config, "batch")) and (self.mono or self.grey_method == "FFT") and config.verbose < 2
 
     def _ingest(self, img):
         """One frame -> float32 device tensor, on the current stream.  Float frames are the reference's call signature
@@ -358,10 +377,6 @@ class BurstPipeline:
             torch.cuda.current_stream(self.device).wait_event(wait_ref)
         return self._robustness([front], accumulate_r, fuse_local_min)[0]
 
-    def fuses_local_min(self):
-        """True when the fused merge can take the un-filtered robustness maps (see merge.can_fuse_local_min)."""
-        return bool(self.config.robustness.enabled) and can_fuse_local_min(self.config, tuple(self.ref.shape))
-
     def process_frames(self, comp_imgs, accumulate_r=None, n_streams=None, fuse_local_min=False, flows=None):
         """process_frame() over a list of frames.  Frames are independent until the merge, so they are
         issued round-robin on `n_streams` HIP streams (config.hip.streams, default 2; 1 for frames >= LARGE_FRAME): the launch-latency-
@@ -398,17 +413,14 @@ class BurstPipeline:
         return chunks
 
     def _chunk_size(self):
-        hip = self.config.get("hip", None) if hasattr(self.config, "get") else None
-        return max(1, min(int(hip.get("chunk", ROB_GROUP)) if hip is not None else ROB_GROUP, _lib.MAX_BATCH))
+        chunk = hip_opt(self.config, "chunk")
+        return max(1, min(ROB_GROUP if chunk is None else int(chunk), _lib.MAX_BATCH))
 
     def _n_streams(self, n_streams):
         if n_streams is None:
-            hip = self.config.get("hip", None) if hasattr(self.config, "get") else None
-            default = DEFAULT_STREAMS
-            ref = getattr(self, "ref", None)
-            if ref is not None and ref.shape[0] * ref.shape[1] >= LARGE_FRAME:
-                default = 1
-            n_streams = int(hip.get("streams", default)) if hip is not None else default
+            n_streams = hip_opt(self.config, "streams")
+        if n_streams is None:
+            n_streams = 1 if self.ref is not None and self.ref.numel() >= LARGE_FRAME else DEFAULT_STREAMS
         return max(1, int(n_streams))
 
     def _on_streams(self, n, n_streams, serial, work):
@@ -459,7 +471,7 @@ class BurstPipeline:
 
 
 _main_runners = []  # [(config, ConfigWatch, HostBurstRunner)], most recently used last
-_main_runners_lock = __import__("threading").Lock()  # main() may be called from several threads
+_main_runners_lock = threading.Lock()  # main() may be called from several threads
 
 
 def _drop_host_runners():
@@ -470,9 +482,7 @@ def _drop_host_runners():
         runner.close()
 
 
-import atexit as _atexit  # noqa: E402
-
-_atexit.register(_drop_host_runners)
+atexit.register(_drop_host_runners)
 
 
 def _host_runner(config, device):
@@ -522,18 +532,7 @@ def main(ref_img, comp_imgs, config, *, _no_runner=False):
     verbose = config.verbose >= 1
     debug_mode = bool(config.debug)
     debug_dict = {"robustness": [], "flow": []}
-    denoiser_on = denoiser_enabled(config)
-    accumulate_r = denoiser_on or bool(config.robustness.save_mask)
-    hip_cfg = config.get("hip", None) if hasattr(config, "get") else None
-    fused = True if hip_cfg is None else bool(hip_cfg.get("fused_merge", True))
-    # Denoiser on (round 6): the comp frames still go through the batched front end and ONE fused merge launch — without the
-    # reference frame and without normalising —, the float64 robustness sum is one pass over the frames' maps
-    # (hhsr_rob_sum), then the reference's sequential tail: merge_ref with the decision map (its overwrite / widen rules,
-    # merge.py:223-228) and divide.  Until now this configuration ran the per-frame operator path: a read-modify-write of
-    # the accumulators and of a float64 torch tensor per frame.
-    den_fused = fused and denoiser_on and can_fuse_acc_r(config) and n_images_of(comp_imgs) > 0 \
-        and not (config.verbose >= 1 or bool(config.debug))
-    fused = fused and not denoiser_on
+    denoiser_on, accumulate_r = accumulation(config)
 
     if verbose:
         torch.cuda.synchronize()
@@ -543,11 +542,11 @@ def main(ref_img, comp_imgs, config, *, _no_runner=False):
     dev = pipe.device
     H, W = pipe.ref.shape
     sH, sW = pipe.output_size()
+    fused, batch, fuse_acc, fuse_min, den_fused = main_plan(config, (H, W), len(comp_imgs), denoiser_on, accumulate_r)
     # the denoiser DECIDES on the accumulated robustness: float64 sum like the reference's (robustness.RobustnessSum); a sum
     # that is only reported (save_mask) stays the float32 sum of the kernels
     acc_sum = RobustnessSum((H, W), dev) if denoiser_on else None
     accumulated_r = torch.zeros((H, W), dtype=torch.float32, device=dev) if (accumulate_r and not denoiser_on) else None
-    fuse_acc = accumulate_r and fused and can_fuse_acc_r(config) and n_images_of(comp_imgs) > 0
     num = torch.empty((sH, sW, 3), dtype=torch.float32, device=dev)
     den = None
     if den_fused:
@@ -561,22 +560,15 @@ def main(ref_img, comp_imgs, config, *, _no_runner=False):
 
     frames = []
     n_images = len(comp_imgs)
-    fuse_min = False
-    if fused and not verbose and not debug_mode:
-        # the x2 merge kernel takes the 5x5 local minimum of the robustness itself (one pass and 8 B/pixel less per
-        # frame); a separately accumulated robustness map needs the filtered maps
-        fuse_min = pipe.fuses_local_min() and (fuse_acc or not accumulate_r)
+    if batch:
+        # the x2 / x3 merge kernels take the 5x5 local minimum of the robustness themselves (one pass and 8 B/pixel less
+        # per frame); a separately accumulated robustness map needs the filtered maps
         # (page-locked host frames: all uploads are queued now, back to back — BurstPipeline.prefetch)
         frames = pipe.process_frames([comp_imgs[i] for i in range(n_images)], None if fuse_acc else accumulated_r,
                                      fuse_local_min=fuse_min)
+        if den_fused:  # the float64 sum takes the minimum on the way in (HHSR_ROB_SUM_MIN5): the filtered maps are never written
+            acc_sum.add_many([f[3] for f in frames], unfiltered=fuse_min)
         n_images = 0  # the per-frame loop below is the verbose / debug / sequential-merge path
-    elif den_fused:
-        # the merge kernel takes the 5x5 minimum itself where it can (x2 / x3 kernels); the float64 sum then takes it on
-        # the way in (HHSR_ROB_SUM_MIN5): the filtered maps are never written
-        fuse_min = pipe.fuses_local_min()
-        frames = pipe.process_frames([comp_imgs[i] for i in range(n_images)], None, fuse_local_min=fuse_min)
-        acc_sum.add_many([f[3] for f in frames], unfiltered=fuse_min)
-        n_images = 0
     for im_id in range(n_images):
         if verbose:
             torch.cuda.synchronize()
@@ -715,10 +707,8 @@ def process(burst_path, config):
         ref_raw = normalize_burst(np.asarray(ref_raw), burst["black_levels"], burst["white_level"],
                                   burst["white_balance"], burst["cfa_pattern"])
         raw_comp = [np.asarray(f) for f in raw_comp]
-        hip = dict(config.get("hip", None) or {})
-        hip["raw_norm"] = {"black_levels": [float(v) for v in list(burst["black_levels"])[:3]],
-                           "white_level": float(burst["white_level"])}
-        config.hip = hip
+        raw_norm = {"black_levels": [float(v) for v in list(burst["black_levels"])[:3]], "white_level": float(burst["white_level"])}
+        config.hip = dict(getattr(config, "hip", None) or {}, raw_norm=raw_norm)  # (a fresh mapping: the caller's is not edited)
         brightness_src = ref_raw.mean().item()
     else:
         ref_raw = np.asarray(ref_raw, dtype=np.float32) if not torch.is_tensor(ref_raw) else ref_raw

@@ -335,3 +335,117 @@ def test_environment_reads_are_the_allowlisted_ones():
                      "HHSR_GREY_PLAN",                                       # tests: the library's FFT plans
                      "HHSR_LIB",                                             # another build of the library (tools/ab.sh)
                      "HHSR_LATE_FORK"}                                       # out of the early-fork ordering contract
+
+
+def test_config_hip_is_read_in_one_place():
+    """config.hip is read through config.hip_opt alone: no other module of the package spells the lookup (and with it a
+    knob's default) out again."""
+    import glob
+    import os
+
+    pkg = os.path.dirname(hsr.__file__)
+    files = glob.glob(os.path.join(pkg, "*.py"))
+    assert len(files) > 15
+    hits = []
+    for f in files:
+        with open(f, encoding="utf-8") as fh:
+            if 'get("hip"' in fh.read():
+                hits.append(os.path.basename(f))
+    assert hits == ["config.py"]
+
+
+HIP_DEFAULTS = {"graph": True, "batch": True, "fused_merge": True, "fused_align": True, "weight_fp64": False,
+                "merge_kernel": "auto", "strategy": "rows", "stage_frames": 0, "chunk": None, "streams": None,
+                "merge_chain": None, "merge_link_after": None, "host_chunk_sizes": None, "inject_flows": None,
+                "raw_norm": None, "max_flow": None, "align_cost": None}
+
+
+class _GetConfig:
+    """A configuration that is no mapping but has its own get(): hands out `hip` as the plain dict it was given."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def get(self, k, default=None):
+        return self.__dict__.get(k, default)
+
+
+def test_hip_opt():
+    import types
+    from handheld_super_resolution.config import HIP_KNOBS, hip_opt
+
+    assert HIP_KNOBS == HIP_DEFAULTS and len(HIP_KNOBS) == 17
+    with_config = default_config()
+    with_config.hip = {"not_a_knob": 1}  # (unknown keys are ignored)
+    assert type(with_config.hip) is Config
+    with_dict = _GetConfig(hip={"not_a_knob": 1})
+    assert type(with_dict.get("hip")) is dict
+    no_get = types.SimpleNamespace(hip={"graph": False, "chunk": 2})  # no .get: the build's switches cannot be reached
+    for cfg in (default_config(), default_config(hip={}), with_config, with_dict, no_get, _GetConfig()):
+        for name, want in HIP_DEFAULTS.items():
+            got = hip_opt(cfg, name)
+            assert got is want or (got == want and type(got) is type(want)), (name, got)
+    for cfg in (with_config, with_dict):  # read at call time: the mapping is edited in place
+        cfg.get("hip")["graph"] = False
+        cfg.get("hip")["chunk"] = 3
+        cfg.get("hip")["raw_norm"] = {"black_levels": [64.0] * 3, "white_level": 1023.0}
+        assert hip_opt(cfg, "graph") is False and hip_opt(cfg, "chunk") == 3
+        assert hip_opt(cfg, "raw_norm")["white_level"] == 1023.0
+        assert hip_opt(cfg, "batch") is True and hip_opt(cfg, "streams") is None
+    for cfg in (default_config(), with_config, with_dict, no_get):
+        with pytest.raises(KeyError):
+            hip_opt(cfg, "fused_merg")
+
+
+# (id, changes, "off" | "save_mask" | "den", main(): batch path / fuse_acc / fuse_min / den_fused, a rank of the multi-GPU
+# strategies: fuse_acc / fuse_min) — derived by reading main(), HostBurstRunner._capture, HipEngine.partial and SlabWork
+# as they were before the rule had one home
+FUSION_CASES = [
+    ("1", {}, "off", "TFTF", "FT"),
+    ("2", {}, "save_mask", "TTTF", "TT"),
+    ("3", {"n_comp": 0}, "save_mask", "TFFF", "FF"),
+    ("4", {"scale": 1.5}, "save_mask", "TFFF", "FF"),
+    ("5", {}, "den", "TFTT", "FF"),
+    ("6", {"verbose": 1}, "den", "FFFF", "FF"),
+    ("7", {"debug": True}, "den", "FFFF", "FF"),
+    ("8", {"scale": 1.5}, "den", "FFFF", "FF"),
+    ("9", {"hip": {"fused_merge": False}}, "save_mask", "FFFF", "TT"),
+    ("10", {"hip": {"weight_fp64": True}}, "off", "TFFF", "FF"),
+    ("11a", {"hip": {"merge_kernel": "tile"}}, "off", "TFFF", "FF"),
+    ("11b", {"hip": {"merge_kernel": "x2_v1"}}, "off", "TFTF", "FT"),
+    ("12a", {"scale": 3}, "off", "TFTF", "FT"),
+    ("12b", {"scale": 3, "shape": (64, 66)}, "off", "TFFF", "FF"),
+    ("13", {"ts": 8}, "off", "TFFF", "FF"),
+    ("14", {"rob": False}, "off", "TFFF", "FF"),
+    ("15a", {"mode": "grey"}, "off", "TFTF", "FT"),
+    ("15b", {"mode": "grey", "scale": 3}, "off", "TFFF", "FF"),
+    ("15c", {"mode": "grey", "hip": {"merge_kernel": "x2_v1"}}, "off", "TFFF", "FF"),
+    ("16", {"verbose": 1}, "save_mask", "FTFF", "TT"),
+]
+
+
+@pytest.mark.parametrize("case", FUSION_CASES, ids=[c[0] for c in FUSION_CASES])
+def test_merge_fusion_decisions(case):
+    """What a burst's merge fuses, per configuration: the plan of main() and the rule the host-resident runner and both
+    multi-GPU strategies share (merge.merge_fusions) against the table of the cases."""
+    from handheld_super_resolution.merge import merge_fusions
+    from handheld_super_resolution.super_resolution import accumulation, main_plan
+
+    _, ch, acc, want_main, want_rank = case
+    cfg = base_config(ts=ch.get("ts", 16), scale=ch.get("scale", 2))
+    assert cfg.exif.cfa_pattern == [[0, 1], [1, 2]] and cfg.verbose == 0 and not cfg.debug and "hip" not in cfg
+    cfg.verbose, cfg.debug, cfg.mode = ch.get("verbose", 0), ch.get("debug", False), ch.get("mode", "bayer")
+    cfg.robustness.enabled = ch.get("rob", True)
+    cfg.robustness.save_mask = acc == "save_mask"
+    cfg.accumulated_robustness_denoiser.enabled = cfg.accumulated_robustness_denoiser.merge.enabled = acc == "den"
+    cfg.hip = ch.get("hip", {})
+    shape, n_comp = ch.get("shape", (64, 64)), ch.get("n_comp", 3)
+    denoiser_on, accumulate_r = accumulation(cfg)
+    assert (denoiser_on, accumulate_r) == (acc == "den", acc != "off")
+    fused, *plan = main_plan(cfg, shape, n_comp, denoiser_on, accumulate_r)
+    assert all(type(v) is bool for v in (fused, *plan))
+    assert "".join("FT"[v] for v in plan) == want_main
+    assert fused == (acc != "den" and cfg.hip.get("fused_merge", True))
+    rank = merge_fusions(cfg, shape, n_comp, accumulate_r, denoiser_on)
+    assert all(type(v) is bool for v in rank)
+    assert "".join("FT"[v] for v in rank) == want_rank
