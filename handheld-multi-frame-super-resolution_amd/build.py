@@ -31,6 +31,7 @@ SOURCES = {
     "hhsr_fft.hip": ["-fno-slp-vectorize"],
     "hhsr_io.hip": ["-ffp-contract=off"],
     "hhsr_post.hip": ["-ffp-contract=off"],
+    "hhsr_tonemap.hip": ["-ffp-contract=off"],  # the Mertens weight maps are a decision stage (exact float32 association)
 }
 
 

@@ -157,13 +157,11 @@ __device__ __forceinline__ size_t oriented_index(int y, int x, int H, int W, int
     }
 }
 
-// pass 2: Gaussian along x of pass 1 (sharpening), result = c + (c - blurred) amount, devignetting, clip, gamma, clip,
-// store at the oriented position.  Without sharpening this is the only pass.
-__global__ void __launch_bounds__(256) k_post_finish(const float* __restrict__ img, const float* __restrict__ tmp,
-                                                      float* __restrict__ out, PostArgs a, const double* __restrict__ taps) {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= a.W || y >= a.H) return;
-    float c[3];
+// One pixel up to the point where the image is finished but not yet clipped: colour matrix + clip, Gaussian along x of
+// pass 1 and c + (c - blurred) amount (sharpening), devignetting.  c: the float32 image; d: the float64 image the
+// reference carries once devignetting ran (float64 gain x float32 image), d = c otherwise.
+__device__ __forceinline__ void post_pixel(const float* __restrict__ img, const float* __restrict__ tmp, const PostArgs& a,
+                                           const double* __restrict__ taps, int x, int y, float c[3], double d[3]) {
     load_ccm(img, ((size_t)y * a.W + x) * 3, a, c);
     if (a.do_sharpen) {
         double acc[3] = {0.0, 0.0, 0.0};
@@ -176,7 +174,8 @@ __global__ void __launch_bounds__(256) k_post_finish(const float* __restrict__ i
 #pragma unroll
         for (int k = 0; k < 3; ++k) c[k] = c[k] + (c[k] - (float)acc[k]) * a.amount;  // float32, no clipping (preserve_range)
     }
-    double d[3] = {(double)c[0], (double)c[1], (double)c[2]};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) d[k] = (double)c[k];
     if (a.do_devignette) {  // (2 - cos(|ly| |lx|)^4) with ly in +- h/w pi/2, lx in +- pi/2 (raw2rgb.py:198-204); float64
         const double hw = (double)a.H / (double)a.W * 1.57079632679489661923;
         const double ly = a.H > 1 ? fabs(-hw + 2.0 * hw * (double)y / (double)(a.H - 1)) : hw;
@@ -186,6 +185,16 @@ __global__ void __launch_bounds__(256) k_post_finish(const float* __restrict__ i
 #pragma unroll
         for (int k = 0; k < 3; ++k) d[k] *= gain;
     }
+}
+
+// pass 2: post_pixel, clip, gamma, clip, store at the oriented position.  Without sharpening this is the only pass.
+__global__ void __launch_bounds__(256) k_post_finish(const float* __restrict__ img, const float* __restrict__ tmp,
+                                                      float* __restrict__ out, PostArgs a, const double* __restrict__ taps) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= a.W || y >= a.H) return;
+    float c[3];
+    double d[3];
+    post_pixel(img, tmp, a, taps, x, y, c, d);
     const size_t o = oriented_index(y, x, a.H, a.W, a.orientation) * 3;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -201,6 +210,41 @@ __global__ void __launch_bounds__(256) k_post_finish(const float* __restrict__ i
         }
         out[o + k] = v;
     }
+}
+
+// pass 2 for tone mapping: post_pixel, then the uint8 exposures e_t = rint(clip(image t, 0, 1) 255), half to even, of
+// the UNCLIPPED image (raw2rgb.py:161-162, skimage img_as_ubyte) in the precision the image has upstream: float32, or
+// float64 once devignetting ran.  A NaN pixel (no sample of a colour, D6) has no uint8 value upstream: 0 here.
+struct ExposeArgs {
+    double t[HHSR_MAX_EXPOSURES];
+    int n;
+};
+
+__global__ void __launch_bounds__(256) k_post_expose(const float* __restrict__ img, const float* __restrict__ tmp,
+                                                      uint8_t* __restrict__ expo, PostArgs a, ExposeArgs e,
+                                                      const double* __restrict__ taps) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= a.W || y >= a.H) return;
+    float c[3];
+    double d[3];
+    post_pixel(img, tmp, a, taps, x, y, c, d);
+    const size_t plane = (size_t)a.H * a.W, o = (size_t)y * a.W + x;
+#pragma unroll
+    for (int i = 0; i < HHSR_MAX_EXPOSURES; ++i)
+        if (i < e.n) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                int v;
+                if (a.do_devignette) {
+                    const double t = rint(clip01d(d[k] * e.t[i]) * 255.0);
+                    v = t == t ? (int)t : 0;
+                } else {
+                    const float t = rintf(clip01(c[k] * (float)e.t[i]) * 255.f);
+                    v = t == t ? (int)t : 0;
+                }
+                expo[((size_t)i * plane + o) * 3 + k] = (uint8_t)v;
+            }
+        }
 }
 
 // [H][W] map (accumulated robustness) to its oriented position
@@ -254,6 +298,35 @@ extern "C" int hhsr_postprocess(const float* image, float* tmp, float* out, int 
     hipStream_t s = (hipStream_t)stream;
     if (a.do_sharpen) hipLaunchKernelGGL(k_post_vblur, grid, block, 0, s, image, tmp, a, taps);
     hipLaunchKernelGGL(k_post_finish, grid, block, 0, s, image, tmp, out, a, taps);
+    HHSR_LAUNCHED();
+}
+
+extern "C" int hhsr_post_expose(const float* image, float* tmp, int H, int W, const float* cam2rgb, int do_sharpen,
+                                double amount, const double* taps, int radius, int do_devignette, const double* times,
+                                int n, uint8_t* exposures, void* stream) {
+    HHSR_ARG(image && exposures && times && H > 0 && W > 0);
+    HHSR_ARG(n >= 1 && n <= HHSR_MAX_EXPOSURES);
+    HHSR_ARG((size_t)H * W * 3 < ((size_t)1 << 31));
+    HHSR_ARG((const void*)exposures != (const void*)image && (const void*)exposures != (const void*)tmp);
+    HHSR_ARG(!do_sharpen || (tmp && taps && radius >= 0 && radius <= 64 && tmp != image));
+    PostArgs a;
+    a.do_ccm = cam2rgb != nullptr;
+    for (int k = 0; k < 9; ++k) a.ccm[k] = cam2rgb ? cam2rgb[k] : (k % 4 == 0 ? 1.f : 0.f);
+    a.do_sharpen = do_sharpen != 0;
+    a.do_devignette = do_devignette != 0;
+    a.do_gamma = 0;
+    a.amount = (float)amount;
+    a.radius = radius;
+    a.H = H;
+    a.W = W;
+    a.orientation = 1;
+    ExposeArgs e;
+    e.n = n;
+    for (int i = 0; i < HHSR_MAX_EXPOSURES; ++i) e.t[i] = i < n ? times[i] : 0.0;
+    const dim3 grid(hhsr_cdiv(W, 64), hhsr_cdiv(H, 4)), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    if (a.do_sharpen) hipLaunchKernelGGL(k_post_vblur, grid, block, 0, s, image, tmp, a, taps);
+    hipLaunchKernelGGL(k_post_expose, grid, block, 0, s, image, (const float*)tmp, exposures, a, e, taps);
     HHSR_LAUNCHED();
 }
 

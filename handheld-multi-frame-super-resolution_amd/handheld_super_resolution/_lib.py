@@ -19,6 +19,8 @@ DP = C.POINTER(C.c_double)
 FP = C.POINTER(C.c_float)
 PP = C.POINTER(C.c_void_p)
 I32P = C.POINTER(C.c_int32)
+SZ = C.c_size_t
+SZP = C.POINTER(C.c_size_t)
 
 # name -> argtypes (all return int)
 _SIGS = {
@@ -65,6 +67,9 @@ _SIGS = {
     "hhsr_frame_count_denoise": [P, P, I, I, P, I, I, D, I, D, D, I, P],
     "hhsr_postprocess": [P, P, P, I, I, FP, I, D, P, I, I, I, I, P],
     "hhsr_orient_plane": [P, P, I, I, I, P],
+    "hhsr_tonemap_workspace": [I, I, I, SZP, I32P],
+    "hhsr_post_expose": [P, P, I, I, FP, I, D, P, I, I, DP, I, P, P],
+    "hhsr_mertens": [P, I, I, I, P, SZ, P, P, I, P],
     "hhsr_merge_burst": [PP, PP, PP, PP, I, I, I, I, I, I, I, P, P, U8P, D, I, I, P, P, P, I, I, I, I, I, P],
     "hhsr_clock_probe": [P, L, P],
     "hhsr_merge_burst_chain": [PP, PP, PP, PP, I, I, I, I, I, I, I, P, P, U8P, D, I, I, P, P, P, I, I, P, I, P],
@@ -74,6 +79,7 @@ MERGE_LOAD_ACC, MERGE_DO_REF, MERGE_DIVIDE, MERGE_STORE_DEN = 1, 2, 4, 8
 MERGE_LOCAL_MIN, MERGE_STORE_CLASSES, MERGE_LOAD_CLASSES = 16, 32, 64
 MAX_FRAMES = 64
 MAX_BATCH = 8  # HHSR_MAX_BATCH: frames per launch of the batched front-end entry points
+MAX_EXPOSURES = 4  # HHSR_MAX_EXPOSURES: exposures per hhsr_post_expose / hhsr_mertens call
 GREY_INFO_LEN = 48  # HHSR_GREY_INFO_LEN: values of the record of hhsr_grey_plan_query / hhsr_grey_plan_info
 
 _lib = None

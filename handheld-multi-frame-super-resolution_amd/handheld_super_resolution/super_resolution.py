@@ -746,7 +746,7 @@ def process(burst_path, config):
     if pp.enabled:
         out = raw2rgb.postprocess(burst.get("rawpy_image", None), out, pp.do_color_correction, pp.do_tonemapping,
                                   pp.do_gamma_correction, pp.sharpening, pp.do_devignetting, burst.get("xyz2cam", None),
-                                  orientation=ori)
+                                  orientation=ori, restated_tonemapping=True)
     else:
         out = apply_orientation(out, ori)
     output_image = out.cpu().numpy()

@@ -42,6 +42,7 @@ extern "C" {
 #define HHSR_MAX_TAPS 33      /* Gaussian taps: 4*factor+1, factor <= 8 */
 #define HHSR_MAX_FRAMES 64    /* frames per hhsr_merge_burst launch */
 #define HHSR_MAX_BATCH 8      /* frames per launch of the batched front-end entry points (hhsr_*_batch) */
+#define HHSR_MAX_EXPOSURES 4  /* exposures per hhsr_post_expose / hhsr_mertens call */
 
 const char* hhsr_version(void);
 const char* hhsr_last_error(void);
@@ -398,12 +399,48 @@ int hhsr_frame_count_denoise(const float* image, float* out, int H, int W, const
  * optional unsharp mask (skimage.filters.unsharp_mask = scipy.ndimage.gaussian_filter, mode "reflect": DEVICE double
  * taps[2 radius + 1], rows first, float64 accumulation, float32 intermediate in tmp [H][W][3]; result = c + (c - blur)
  * amount), optional devignetting (raw2rgb.py:198-204), clip, optional gamma 1/2.2, clip; the result is stored at its
- * EXIF-oriented position (utils_image.py:12-55; orientation 5..8: out is [W][H][3]).  Tone mapping is out of scope. */
+ * EXIF-oriented position (utils_image.py:12-55; orientation 5..8: out is [W][H][3]).  Tone mapping (do_tonemapping) sits between the
+ * devignetting and the first clip: hhsr_post_expose + hhsr_mertens below, then this call with every earlier stage off. */
 int hhsr_postprocess(const float* image, float* tmp, float* out, int H, int W, const float* cam2rgb, int do_sharpen,
                      double amount, const double* taps, int radius, int do_devignette, int do_gamma, int orientation,
                      void* stream);
 /* float32 [H][W] plane (accumulated robustness) to its EXIF-oriented position (utils_image.py:12-55). */
 int hhsr_orient_plane(const float* in, float* out, int H, int W, int orientation, void* stream);
+
+/* ---- tone mapping (raw2rgb.py:153-170): exposure fusion of the finished image, then the smoothstep curve -------------
+ * The reference builds uint8 exposures of the image at times (1, 0.5, 2), fuses them with cv2.createMergeMertens() and
+ * applies 3 r^2 - 2 r^3.  OpenCV is not part of this build: the contract is OpenCV 4.x MergeMertens with its default
+ * weights (contrast 1, saturation 1, exposure 0) restated operation by operation — tests/mertens_ref.py is the NumPy
+ * form the kernels are tested against — and has not been compared with a cv2 run (PARITY.md).  All images here are
+ * COMPACT (no pitch).
+ *
+ * hhsr_post_expose: hhsr_postprocess's colour matrix + clip, unsharp mask and devignetting, bit for bit, then instead
+ * of clip / gamma / orientation the exposures e_i = rint(clip(image times[i], 0, 1) 255), half to even, uint8
+ * [n][H][W][3] (skimage img_as_ubyte).  The image is NOT clipped before it is scaled, and the arithmetic has the
+ * precision the image has upstream: float32, or float64 when do_devignette (float64 gain x float32 image).  times:
+ * HOST double[n], 1 <= n <= HHSR_MAX_EXPOSURES.  A NaN pixel gives 0.  tmp as for hhsr_postprocess.
+ *
+ * hhsr_mertens: exposures uint8 [n][H][W][3] -> out float32 [H][W][3].
+ *   I = float(e) * float(1 / 255);                       weight maps in float32, this association, no FMA:
+ *   grey = (I0 0.299f + I1 0.587f) + I2 0.114f;  contrast = |(((g[y-1,x] + g[y,x-1]) + g[y,x] (-4)) + g[y,x+1]) + g[y+1,x]|
+ *   (reflect-101 border);  mean = ((I0 + I1) + I2) float(1 / 3);  saturation = sqrt((d0 d0 + d1 d1) + d2 d2), d = I - mean;
+ *   w = contrast saturation + 1e-12f;  wn_i = w_i / ((w_0 + w_1) + w_2 ...)   (sqrt and division correctly rounded).
+ *   levels L = floor(log2(min(H, W))) (OpenCV: int(logf(float(min)) / logf(2.f)), which at a power of two depends on
+ *   the platform's logf); Gaussian pyramids of I_i and wn_i (pyrDown: [1 4 6 4 1] / 16 per
+ *   axis at 2 i, size (n + 1) / 2, reflect-101); out_l = sum_i (G_l - pyrUp(G_{l+1})) W_l + pyrUp(out_{l+1}), out_L =
+ *   sum_i G_L W_L (pyrUp: out[2i] = (s[i-1] + 6 s[i] + s[i+1]) / 8, out[2i+1] = (s[i] + s[i+1]) / 2 per axis, s[-1] = s[1],
+ *   s[n] = s[n-1]); out = out_0, through 3 r^2 - 2 r^3 when `smoothstep`.  On pixels whose three channels are equal
+ *   after quantisation the saturation is 0 or one rounding error, so the weights there are decided by float32 rounding
+ *   alone: that is why the association above is part of the contract.
+ * weights_out: optional float32 [n][H][W], the normalised weights wn.  workspace: DEVICE scratch of at least the
+ * `bytes` hhsr_tonemap_workspace reports (4-byte aligned), overlapping none of the other arguments (error -1).
+ * hhsr_tonemap_workspace is host-only (no HIP call): bytes and pyramid levels L for an image. */
+int hhsr_tonemap_workspace(int H, int W, int n, size_t* bytes, int* levels);
+int hhsr_post_expose(const float* image, float* tmp, int H, int W, const float* cam2rgb, int do_sharpen, double amount,
+                     const double* taps, int radius, int do_devignette, const double* times, int n, uint8_t* exposures,
+                     void* stream);
+int hhsr_mertens(const uint8_t* exposures, int n, int H, int W, void* workspace, size_t workspace_bytes,
+                 float* weights_out, float* out, int smoothstep, void* stream);
 
 /* ---- measurement support ------------------------------------------------------------------------------------------
  * Shader-clock probe: one wave that sleeps for `ticks_100mhz` ticks of the constant 100 MHz counter and stores
