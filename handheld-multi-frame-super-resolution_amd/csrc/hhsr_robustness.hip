@@ -4,6 +4,7 @@
 //   k_frame_stats raw -> guide (LDS tile) -> 3x3 mean/variance at guide resolution        (hhsr_kernels.hip)
 //   k_rob_frame   fused: Dodgson warp-upsample of the frame's means, |d mu|, noise-model shrink,
 //                 S lookup, threshold -> R at raw resolution                               (no temporaries)
+//   k_rob_frames_row4<VEC>  the same in float32 for tile sizes that are multiples of 16, up to 4 frames per launch
 //   k_local_min5  5x5 minimum through an LDS tile
 // Arithmetic follows the reference's Numba typing: float64 weights and noise-model
 // maths, float32 storage and float32 running sums that are rounded after every tap.
@@ -303,7 +304,6 @@ __global__ void __launch_bounds__(256) k_rob_frame(const float* __restrict__ cm,
 // coalesced loads; the 27 taps of every pixel come from LDS: ~8 vector loads per pixel instead of 41.
 constexpr int RF_T = 16;               // a 16-column group lies inside one flow tile (ts % 16 == 0)
 constexpr int RF_BX = 32, RF_BY = 32;  // raw pixels per workgroup (2 x 2 sub-tiles of 16 x 16)
-constexpr int RF_NK = 4;               // pixels per thread (rows ly + 8k)
 constexpr int RF_WN = 11;              // guide window per sub-tile: 16/2 + 3 rows and columns
 
 // One axis of the guide-image position of raw pixel p displaced by the tile's flow f:
@@ -348,7 +348,7 @@ __device__ __forceinline__ void dodgson3(float r, int c, int len, float w[3]) {
     w[2] = c + 1 <= len - 1 ? op : inner;
 }
 
-// Arithmetic of this fused kernel (vs the reference's Numba typing):
+// Arithmetic of rob_row4 (vs the reference's Numba typing):
 //   * the in/out-of-image test, the window centre (round-half-even) and the clamped taps: exact integer /
 //     predicate form of the reference's float64 expressions (rob_axis / rob_centre) — identical decisions;
 //   * Dodgson weights and the weighted mean: float32 FMAs.  The reference evaluates the weights in
@@ -360,135 +360,8 @@ __device__ __forceinline__ void dodgson3(float r, int c, int len, float w[3]) {
 //     (1 ulp each; relative error ~2e-7 on values that feed exp(-d^2/sigma^2)); Inf / NaN propagate like the
 //     IEEE divisions they replace, so the D6 border and out-of-image pixels still end at R = 0.
 // Net effect on R: <= 1e-4 absolute on the few pixels in the transition band 0 < R < 1 (tests: 1e-4).
-// The kernel is VALU-bound (it was ~550 instructions per pixel, 69 of them float64, before this form).
-// Workgroup = 32 x 32 raw pixels = 2 x 2 sub-tiles of 16 x 16 (each inside one flow tile, own guide window);
-// a thread owns 4 pixels (rows ly, ly+8, ly+16, ly+24).  One short dependent chain (flow -> window origin ->
-// guide loads -> LDS) per 1024 pixels and 20 independent plane loads in flight per thread: with one pixel per
-// thread the kernel was bound by that chain's latency (3 TB/s of plane traffic at 8 workgroups per CU).
-__global__ void __launch_bounds__(256) k_rob_frame_tile(const float* __restrict__ cm, int lh, int lw,
-                                                         const float* __restrict__ rmean,
-                                                         const float* __restrict__ ssq,
-                                                         const uint32_t* __restrict__ cidx,
-                                                         const float2* __restrict__ flow, int nx, int ts,
-                                                         const float* __restrict__ S,
-                                                         const double* __restrict__ difc, double t,
-                                                         float* __restrict__ R, int H, int W) {
-    __shared__ float s_g[2][2][3][RF_WN][RF_WN + 2];
-    const int lx_ = threadIdx.x & (RF_BX - 1), ly_ = threadIdx.x >> 5;
-    const int grp = lx_ >> 4;  // 16-column group
-    const int bx = blockIdx.x * RF_BX + grp * RF_T, by = blockIdx.y * RF_BY;
-    const int x = blockIdx.x * RF_BX + lx_;
-    const int tix = min(bx, W - 1) / ts;
-    RobAxis ay[2], ax[2];
-    int wy0[2], wx0[2];
-    float Sv[2];
-#pragma unroll
-    for (int v = 0; v < 2; ++v) {  // the two sub-tiles of this column group
-        const int tiy = min(by + RF_T * v, H - 1) / ts;
-        const float2 f = flow[(size_t)tiy * nx + tix];
-        Sv[v] = S[(size_t)tiy * nx + tix];
-        ay[v] = rob_axis(f.y);
-        ax[v] = rob_axis(f.x);
-        // window origin from the sub-tile's first pixel (the centre is monotone in the pixel coordinate and
-        // 16 pixels advance it by at most 8, so centre-1 .. centre+1 stays inside 11 x 11 entries)
-        float r_;
-        rob_centre(ay[v], by + RF_T * v, lh, wy0[v], r_);
-        rob_centre(ax[v], bx, lw, wx0[v], r_);
-        wy0[v] = clampi(wy0[v], -4, lh + 4) - 1;
-        wx0[v] = clampi(wx0[v], -4, lw + 4) - 1;
-    }
-    const size_t gplane = (size_t)lh * lw;
-    const int tg = (lx_ & (RF_T - 1)) + RF_T * ly_;  // 0..127 within the column group
-    constexpr int WSZ = 3 * RF_WN * RF_WN, NST = (WSZ + 127) / 128;
-    float st[2][NST];
-#pragma unroll
-    for (int v = 0; v < 2; ++v)
-#pragma unroll
-        for (int u = 0; u < NST; ++u) {
-            const int p = tg + 128 * u;
-            if (p < WSZ) {
-                const int c = p / (RF_WN * RF_WN), q = p - c * (RF_WN * RF_WN);
-                const int i = q / RF_WN, j = q - i * RF_WN;
-                const int gy = clampi(wy0[v] + i, 0, lh - 1), gx = clampi(wx0[v] + j, 0, lw - 1);
-                st[v][u] = cm[c * gplane + (size_t)gy * lw + gx];
-            }
-        }
-    // the reference-frame operands do not depend on the LDS window: issue their loads before the barrier
-    const size_t plane = (size_t)H * W;
-    bool live[RF_NK];
-    size_t o[RF_NK];
-    float rb[RF_NK][3], s_sq[RF_NK];
-    uint32_t ci[RF_NK];
-#pragma unroll
-    for (int k = 0; k < RF_NK; ++k) {
-        const int y = by + ly_ + 8 * k;
-        live[k] = x < W && y < H;
-        o[k] = live[k] ? (size_t)y * W + x : 0;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) rb[k][c] = rmean[c * plane + o[k]];
-        s_sq[k] = ssq[o[k]];
-        ci[k] = cidx[o[k]];
-    }
-#pragma unroll
-    for (int v = 0; v < 2; ++v)
-#pragma unroll
-        for (int u = 0; u < NST; ++u) {
-            const int p = tg + 128 * u;
-            if (p < WSZ) {
-                const int c = p / (RF_WN * RF_WN), q = p - c * (RF_WN * RF_WN);
-                const int i = q / RF_WN, j = q - i * RF_WN;
-                s_g[grp][v][c][i][j] = st[v][u];
-            }
-        }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < RF_NK; ++k) {
-        if (!live[k]) continue;
-        const int v = k >> 1, y = by + ly_ + 8 * k;
-        float d_t[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) d_t[c] = (float)difc[(ci[k] >> (10 * c)) & 1023u];
-        int cy, cx;
-        float ry, rx;
-        const bool iny = rob_centre(ay[v], y, lh, cy, ry), inx = rob_centre(ax[v], x, lw, cx, rx);
-        float cmu[3] = {INFINITY, INFINITY, INFINITY};
-        if (iny && inx) {
-            float wxv[3], wyv[3], b0 = 0.f, b1 = 0.f, b2 = 0.f, wacc = 0.f;
-            dodgson3(rx, cx, lw, wxv);
-            dodgson3(ry, cy, lh, wyv);
-            const int wi0 = cy - 1 - wy0[v], wj0 = cx - 1 - wx0[v];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    const float w = wyv[i] * wxv[j];
-                    b0 = fmaf(s_g[grp][v][0][wi0 + i][wj0 + j], w, b0);
-                    b1 = fmaf(s_g[grp][v][1][wi0 + i][wj0 + j], w, b1);
-                    b2 = fmaf(s_g[grp][v][2][wi0 + i][wj0 + j], w, b2);
-                    wacc += w;
-                }
-            }
-            const float iw = __builtin_amdgcn_rcpf(wacc);
-            cmu[0] = b0 * iw;
-            cmu[1] = b1 * iw;
-            cmu[2] = b2 * iw;
-        }
-        float d_sq = 0.f;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float dp = fabsf(rb[k][c] - cmu[c]);
-            const float dp2 = dp * dp;
-            const float shrink = dp2 * __builtin_amdgcn_rcpf(dp2 + d_t[c] * d_t[c]);
-            d_sq += dp2 * shrink * shrink;
-        }
-        const float e = __builtin_amdgcn_exp2f((-d_sq * __builtin_amdgcn_rcpf(s_sq[k])) * 1.44269504088896341f);
-        double r = (double)(Sv[v] * e) - t;
-        r = r > 0.0 ? r : 0.0;
-        r = r < 1.0 ? r : 1.0;
-        R[o[k]] = (float)r;
-    }
-}
-
+// The tap loop is VALU-bound (it was ~550 instructions per pixel, 69 of them float64, before this form).
+//
 // The 4 horizontally adjacent pixels x0 .. x0 + 3 (x0 % 4 == 0) of one row of a sub-tile, from the sub-tile's guide
 // window `win` ([3][RF_WN][RF_WN + 2], origin (wy0, wx0)): warped guide means -> colour distance -> shrink -> R.
 // Pixels k and k + 2 lie one guide pixel apart with the same sub-pixel phase (l = (p + f + 0.5) / 2 - 0.5), so they
@@ -590,95 +463,19 @@ __device__ __forceinline__ void rob_row4(const float (*win)[RF_WN][RF_WN + 2], c
     }
 }
 
-// Same kernel with a ROW mapping: a thread owns 4 horizontally adjacent pixels of one row (one flow tile, one
-// sub-tile window).  The five reference-frame planes and R move as 16-byte vectors (1 KB per wave instruction
-// instead of 256 B: the dword version streamed at 3.5 TB/s), and the row part of the geometry — in-image test,
-// centre, Dodgson weights in y — is evaluated once per 4 pixels.  Needs W % 4 == 0 and 16-byte aligned planes.
-__global__ void __launch_bounds__(256) k_rob_frame_row4(const float* __restrict__ cm, int lh, int lw,
-                                                         const float* __restrict__ rmean,
-                                                         const float* __restrict__ ssq,
-                                                         const uint32_t* __restrict__ cidx,
-                                                         const float2* __restrict__ flow, int nx, int ts,
-                                                         const float* __restrict__ S,
-                                                         const double* __restrict__ difc, double t,
-                                                         float* __restrict__ R, int H, int W) {
-    __shared__ float s_g[2][2][3][RF_WN][RF_WN + 2];
-    const int lx4 = threadIdx.x & 7, ly_ = threadIdx.x >> 3;  // 8 threads x 4 pixels per row, 32 rows
-    const int grp = lx4 >> 2, v = ly_ >> 4;                   // the thread's 16 x 16 sub-tile
-    const int bid = xcd_remap(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);  // bands of tile rows per XCD
-    const int bxi = bid % gridDim.x, byi = bid / gridDim.x;
-    const int sx0 = bxi * RF_BX + grp * RF_T, sy0 = byi * RF_BY + v * RF_T;
-    const int x0 = bxi * RF_BX + 4 * lx4, y = byi * RF_BY + ly_;
-    const int tix = min(sx0, W - 1) / ts, tiy = min(sy0, H - 1) / ts;
-    const float2 f = flow[(size_t)tiy * nx + tix];
-    const float Sv = S[(size_t)tiy * nx + tix];
-    const RobAxis ay = rob_axis(f.y), ax = rob_axis(f.x);
-    int wy0, wx0;
-    {
-        float r_;
-        rob_centre(ay, sy0, lh, wy0, r_);
-        rob_centre(ax, sx0, lw, wx0, r_);
-        wy0 = clampi(wy0, -4, lh + 4) - 1;
-        wx0 = clampi(wx0, -4, lw + 4) - 1;
-    }
-    const size_t gplane = (size_t)lh * lw;
-    const int tg = (ly_ & (RF_T - 1)) * 4 + (lx4 & 3);  // 0..63 within the sub-tile
-    constexpr int WSZ = 3 * RF_WN * RF_WN, NST = (WSZ + 63) / 64;
-    float st[NST];
-#pragma unroll
-    for (int u = 0; u < NST; ++u) {
-        const int p = tg + 64 * u;
-        if (p < WSZ) {
-            const int c = p / (RF_WN * RF_WN), q = p - c * (RF_WN * RF_WN);
-            const int i = q / RF_WN, j = q - i * RF_WN;
-            const int gy = clampi(wy0 + i, 0, lh - 1), gx = clampi(wx0 + j, 0, lw - 1);
-            st[u] = cm[c * gplane + (size_t)gy * lw + gx];
-        }
-    }
-    const size_t plane = (size_t)H * W;
-    const bool live = x0 < W && y < H;
-    const size_t o = live ? (size_t)y * W + x0 : 0;
-    float4 rb4[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) rb4[c] = *reinterpret_cast<const float4*>(rmean + c * plane + o);
-    const float4 ss4 = *reinterpret_cast<const float4*>(ssq + o);
-    const uint4 ci4 = *reinterpret_cast<const uint4*>(cidx + o);
-#pragma unroll
-    for (int u = 0; u < NST; ++u) {
-        const int p = tg + 64 * u;
-        if (p < WSZ) {
-            const int c = p / (RF_WN * RF_WN), q = p - c * (RF_WN * RF_WN);
-            const int i = q / RF_WN, j = q - i * RF_WN;
-            s_g[grp][v][c][i][j] = st[u];
-        }
-    }
-    __syncthreads();
-    if (!live) return;
-    const float rbk[4][3] = {{rb4[0].x, rb4[1].x, rb4[2].x}, {rb4[0].y, rb4[1].y, rb4[2].y},
-                             {rb4[0].z, rb4[1].z, rb4[2].z}, {rb4[0].w, rb4[1].w, rb4[2].w}};
-    const float ssk[4] = {ss4.x, ss4.y, ss4.z, ss4.w};
-    const uint32_t cik[4] = {ci4.x, ci4.y, ci4.z, ci4.w};
-    float d_t2[4][3], iss[4], out[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float d = (float)difc[(cik[k] >> (10 * c)) & 1023u];
-            d_t2[k][c] = d * d;
-        }
-        iss[k] = __builtin_amdgcn_rcpf(ssk[k]);
-    }
-    rob_row4(s_g[grp][v], ay, ax, wy0, wx0, y, x0, lh, lw, rbk, d_t2, iss, Sv, (float)t, out);
-    *reinterpret_cast<float4*>(R + o) = make_float4(out[0], out[1], out[2], out[3]);
-}
-
-// ---- several frames per launch ------------------------------------------------------------------------------------
-// The reference-frame operands — three upsampled mean planes, sigma^2, the packed curve indices: 20 of the 27 bytes a
-// frame moves per pixel — do not depend on the compared frame, and k_rob_frame_row4 streams them again for every frame of
-// the burst (326 MB per launch at 12 MP, 4.3 TB/s: HBM-bound).  This variant keeps them (and the three d_t lookups
-// per pixel) in registers and loops over up to ROB_GROUP frames of the same burst: per frame only the guide-means
-// window (3 B / pixel) comes in and R (4 B / pixel) goes out.  Same arithmetic per frame: bit-identical to one launch
-// of k_rob_frame_row4 per frame.
+// ---- the fused kernel: a thread per 4 adjacent pixels, several frames per launch -----------------------------------------
+// Workgroup = 32 x 32 raw pixels = 2 x 2 sub-tiles of 16 x 16 (each inside one flow tile, own guide window in LDS); a thread
+// owns 4 horizontally adjacent pixels of one row and evaluates the row part of the geometry — in-image test, centre,
+// Dodgson weights in y — once for them.  The reference-frame operands — three upsampled mean planes, sigma^2, the packed
+// curve indices: 20 of the 27 bytes a frame moves per pixel — do not depend on the compared frame: the kernel keeps them
+// (and the three d_t lookups per pixel) in registers and loops over up to ROB_GROUP frames of the same burst, so that per
+// frame only the guide-means window (3 B / pixel) comes in and R (4 B / pixel) goes out (one launch per frame streamed
+// 326 MB of reference planes per frame at 12 MP, HBM-bound).  The arithmetic of a frame does not depend on the number of
+// frames in the launch, nor on VEC: hhsr_rob_frame is this kernel with one frame, bit for bit.
+// VEC (W % 4 == 0, 16-byte aligned planes): the five reference-frame planes and R move as 16-byte vectors (1 KB per wave
+// instruction instead of 256 B: the dword form streams at 3.5 TB/s).  !VEC (W % 4 == 2 or a plane off the 16-byte grid):
+// dword loads and stores, each guarded by the row's end; a pixel past it is computed from zeros (it lies inside the thread's
+// sub-tile, so its taps stay inside the LDS window) and never stored.
 constexpr int ROB_GROUP = 4;
 struct RobGroup {
     const float* cm[ROB_GROUP];
@@ -688,6 +485,30 @@ struct RobGroup {
     int n;
 };
 
+template <bool VEC, typename V, typename T>
+__device__ __forceinline__ V rob_load4(const T* __restrict__ p, int x0, int W) {
+    if constexpr (VEC) {
+        return *reinterpret_cast<const V*>(p);
+    } else {
+        V v;
+        v.x = x0 < W ? p[0] : T(0);
+        v.y = x0 + 1 < W ? p[1] : T(0);
+        v.z = x0 + 2 < W ? p[2] : T(0);
+        v.w = x0 + 3 < W ? p[3] : T(0);
+        return v;
+    }
+}
+template <bool VEC>
+__device__ __forceinline__ void rob_store4(float* __restrict__ p, const float out[4], int x0, int W) {
+    if constexpr (VEC) {
+        *reinterpret_cast<float4*>(p) = make_float4(out[0], out[1], out[2], out[3]);
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (x0 + q < W) p[q] = out[q];
+    }
+}
+
 // (no occupancy bound: held to 64 VGPRs — 8 waves per SIMD — the kernel spills and takes 505 instead of 222 us per launch;
 // held to 80: 423 us.  The compiler's own choice is 56 VGPRs.)
 // Measured without gain (round 5, after round 4's counters showed 54 % of the wave time parked with the VALU 78 % busy): a
@@ -696,6 +517,7 @@ struct RobGroup {
 // (60 against 56 VGPRs, 14.2 against 7.4 KB of LDS; bit-identical).  The waves do not wait for each other at those
 // barriers; what they wait for is their own dependent chains (27 taps x 4 pixels of FMAs behind 72 LDS reads, 12 v_rcp_f32,
 // 4 v_exp_f32 per thread and frame) — the kernel is at ~6 cycles per VALU instruction like the other tap kernels.
+template <bool VEC>
 __global__ void __launch_bounds__(256) k_rob_frames_row4(RobGroup gq, int lh, int lw, const float* __restrict__ rmean,
                                                           const float* __restrict__ ssq,
                                                           const uint32_t* __restrict__ cidx, int ny, int nx, int ts,
@@ -716,9 +538,9 @@ __global__ void __launch_bounds__(256) k_rob_frames_row4(RobGroup gq, int lh, in
     // per-burst operands of the thread's 4 pixels, once
     float4 rb4[3];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) rb4[c] = *reinterpret_cast<const float4*>(rmean + c * plane + o);
-    const float4 ss4 = *reinterpret_cast<const float4*>(ssq + o);
-    const uint4 ci4 = *reinterpret_cast<const uint4*>(cidx + o);
+    for (int c = 0; c < 3; ++c) rb4[c] = rob_load4<VEC, float4>(rmean + c * plane + o, x0, W);
+    const float4 ss4 = rob_load4<VEC, float4>(ssq + o, x0, W);
+    const uint4 ci4 = rob_load4<VEC, uint4>(cidx + o, x0, W);
     const float rbk[4][3] = {{rb4[0].x, rb4[1].x, rb4[2].x}, {rb4[0].y, rb4[1].y, rb4[2].y},
                              {rb4[0].z, rb4[1].z, rb4[2].z}, {rb4[0].w, rb4[1].w, rb4[2].w}};
     const float ssk[4] = {ss4.x, ss4.y, ss4.z, ss4.w};
@@ -826,7 +648,36 @@ __global__ void __launch_bounds__(256) k_rob_frames_row4(RobGroup gq, int lh, in
         if (!live) continue;
         float out[4];
         rob_row4(s_g[grp][v], ay, ax, wy0, wx0, y, x0, lh, lw, rbk, d_t2, iss, Sv, (float)t, out);
-        *reinterpret_cast<float4*>(gq.R[fr] + o) = make_float4(out[0], out[1], out[2], out[3]);
+        rob_store4<VEC>(gq.R[fr] + o, out, x0, W);
+    }
+}
+
+// The fused kernel needs a 16-column group inside one flow tile and the packed curve indices of hhsr_rob_sigma.
+static bool rob_grouped(int ts, const uint32_t* ref_curve_index, int ncurve) {
+    return ts % RF_T == 0 && ref_curve_index && ncurve <= 1024;
+}
+
+static void rob_frames_launch(const float* const* comp_means, int n_frames, int lh, int lw, const float* ref_means,
+                              const float* ref_sigma_sq, const uint32_t* ref_curve_index, const float* const* flows, int ny,
+                              int nx, int ts, const float* const* S, double Mt, float s1, float s2, const double* diff_curve,
+                              double t, float* const* R, int flow_rows_before, int flow_rows_after, hipStream_t stream) {
+    const int H = 2 * lh, W = 2 * lw;
+    bool vec = W % 4 == 0 && (((uintptr_t)ref_means | (uintptr_t)ref_sigma_sq | (uintptr_t)ref_curve_index) & 15) == 0;
+    for (int n = 0; n < n_frames; ++n) vec = vec && ((uintptr_t)R[n] & 15) == 0;
+    for (int n0 = 0; n0 < n_frames; n0 += ROB_GROUP) {
+        RobGroup g;
+        g.n = n_frames - n0 < ROB_GROUP ? n_frames - n0 : ROB_GROUP;
+        for (int k = 0; k < ROB_GROUP; ++k) {
+            const int n = n0 + (k < g.n ? k : 0);
+            g.cm[k] = comp_means[n];
+            g.flow[k] = reinterpret_cast<const float2*>(flows[n]);
+            g.S[k] = S ? S[n] : nullptr;
+            g.R[k] = R[n];
+        }
+        hipLaunchKernelGGL(vec ? k_rob_frames_row4<true> : k_rob_frames_row4<false>,
+                           dim3(hhsr_cdiv(W, RF_BX), hhsr_cdiv(H, RF_BY)), dim3(256), 0, stream, g, lh, lw, ref_means,
+                           ref_sigma_sq, ref_curve_index, ny, nx, ts, diff_curve, t, H, W, Mt * Mt, s1, s2, flow_rows_before,
+                           flow_rows_after);
     }
 }
 
@@ -838,16 +689,9 @@ extern "C" int hhsr_rob_frame(const float* comp_means, int lh, int lw, const flo
     HHSR_ARG(lh > 0 && lw > 0 && ts > 0 && ncurve > 0);
     const int H = 2 * lh, W = 2 * lw;
     HHSR_ARG(ny * ts >= H && nx * ts >= W);
-    const bool vec4 = W % 4 == 0 && (((uintptr_t)ref_means | (uintptr_t)ref_sigma_sq | (uintptr_t)ref_curve_index |
-                                      (uintptr_t)R) & 15) == 0;
-    if (ts % RF_T == 0 && ref_curve_index && ncurve <= 1024 && vec4)
-        hipLaunchKernelGGL(k_rob_frame_row4, dim3(hhsr_cdiv(W, RF_BX), hhsr_cdiv(H, RF_BY)), dim3(256), 0,
-                           (hipStream_t)stream, comp_means, lh, lw, ref_means, ref_sigma_sq, ref_curve_index,
-                           reinterpret_cast<const float2*>(flow), nx, ts, S, diff_curve, t, R, H, W);
-    else if (ts % RF_T == 0 && ref_curve_index && ncurve <= 1024)
-        hipLaunchKernelGGL(k_rob_frame_tile, dim3(hhsr_cdiv(W, RF_BX), hhsr_cdiv(H, RF_BY)), dim3(256), 0,
-                           (hipStream_t)stream, comp_means, lh, lw, ref_means, ref_sigma_sq, ref_curve_index,
-                           reinterpret_cast<const float2*>(flow), nx, ts, S, diff_curve, t, R, H, W);
+    if (rob_grouped(ts, ref_curve_index, ncurve))  // (S given: Mt, s1, s2 and the flow rows are not read)
+        rob_frames_launch(&comp_means, 1, lh, lw, ref_means, ref_sigma_sq, ref_curve_index, &flow, ny, nx, ts, &S, 0.0, 0.f,
+                          0.f, diff_curve, t, &R, 0, 0, (hipStream_t)stream);
     else
         hipLaunchKernelGGL(k_rob_frame, dim3(hhsr_cdiv(W, 64), hhsr_cdiv(H, 4)), dim3(256), 0, (hipStream_t)stream,
                            comp_means, lh, lw, ref_means, ref_sigma_sq, reinterpret_cast<const float2*>(flow), nx, ts,
@@ -865,12 +709,10 @@ extern "C" int hhsr_rob_frames(const float* const* comp_means, int n_frames, int
     HHSR_ARG(ref_means && ref_sigma_sq && diff_curve && lh > 0 && lw > 0 && ts > 0 && ncurve > 0);
     const int H = 2 * lh, W = 2 * lw;
     HHSR_ARG(ny * ts >= H && nx * ts >= W);
-    bool vec4 = W % 4 == 0 && (((uintptr_t)ref_means | (uintptr_t)ref_sigma_sq | (uintptr_t)ref_curve_index) & 15) == 0;
-    for (int n = 0; n < n_frames; ++n) vec4 = vec4 && ((uintptr_t)R[n] & 15) == 0;
-    if (!(ts % RF_T == 0 && ref_curve_index && ncurve <= 1024 && vec4)) {
+    if (!rob_grouped(ts, ref_curve_index, ncurve)) {
         if (!S) {
             hhsr_set_error("hhsr_rob_frames: S = NULL (weights evaluated inside the kernel) needs the grouped kernel: "
-                           "ts %% 16 == 0, W %% 4 == 0, packed curve indices, 16-byte aligned planes");
+                           "ts %% 16 == 0, packed curve indices");
             return -3;
         }
         for (int n = 0; n < n_frames; ++n) {
@@ -880,20 +722,8 @@ extern "C" int hhsr_rob_frames(const float* const* comp_means, int n_frames, int
         }
         return 0;
     }
-    for (int n0 = 0; n0 < n_frames; n0 += ROB_GROUP) {
-        RobGroup g;
-        g.n = n_frames - n0 < ROB_GROUP ? n_frames - n0 : ROB_GROUP;
-        for (int k = 0; k < ROB_GROUP; ++k) {
-            const int n = n0 + (k < g.n ? k : 0);
-            g.cm[k] = comp_means[n];
-            g.flow[k] = reinterpret_cast<const float2*>(flows[n]);
-            g.S[k] = S ? S[n] : nullptr;
-            g.R[k] = R[n];
-        }
-        hipLaunchKernelGGL(k_rob_frames_row4, dim3(hhsr_cdiv(W, RF_BX), hhsr_cdiv(H, RF_BY)), dim3(256), 0,
-                           (hipStream_t)stream, g, lh, lw, ref_means, ref_sigma_sq, ref_curve_index, ny, nx, ts, diff_curve, t,
-                           H, W, Mt * Mt, s1, s2, flow_rows_before, flow_rows_after);
-    }
+    rob_frames_launch(comp_means, n_frames, lh, lw, ref_means, ref_sigma_sq, ref_curve_index, flows, ny, nx, ts, S, Mt, s1, s2,
+                      diff_curve, t, R, flow_rows_before, flow_rows_after, (hipStream_t)stream);
     HHSR_LAUNCHED();
 }
 
@@ -1157,7 +987,7 @@ __global__ void __launch_bounds__(256) k_mono_rob_frame(const float* __restrict_
     R[o] = (float)v;
 }
 
-// The same with the float32 arithmetic of the Bayer kernels (see k_rob_frame_tile: exact integer / predicate geometry,
+// The same with the float32 arithmetic of the Bayer kernels (see rob_row4: exact integer / predicate geometry,
 // float32 Dodgson weights, v_rcp_f32 / v_exp_f32 tail; |dR| <= 1e-4) and a thread per 4 horizontally adjacent pixels
 // (x0 % 4 == 0, ts % 4 == 0: one flow tile).  Pixels k and k + 2 lie one guide pixel apart with the same sub-pixel
 // phase and share the weights; the two phases' 3 x 4 windows overlap in a 3 x 5 window read once from L1 / L2 (the

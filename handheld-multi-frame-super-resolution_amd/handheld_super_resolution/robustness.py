@@ -296,8 +296,8 @@ def compute_robustness_group(comp_imgs, ref_local_means, flows, noise_model, con
     ny, nx, _ = flows[0].shape
     sigma_sq, curve_index = ref_sigma_sq
     # the grouped kernel evaluates the per-tile flow-irregularity weight S itself (one launch less per frame); the
-    # per-frame fall-back kernels of hhsr_rob_frames need the S maps — same test as in the library
-    inline_s = int(ts) % 16 == 0 and W % 4 == 0 and curve_index is not None and diff_curve.numel() <= 1024
+    # generic per-frame kernel of hhsr_rob_frames needs the S maps — same test as in the library
+    inline_s = int(ts) % 16 == 0 and curve_index is not None and diff_curve.numel() <= 1024
     for f in flows:
         _check_flow_view(f, flow_rows)
     S = None if inline_s else [compute_s(f, t.Mt, t.s1, t.s2, flow_rows) for f in flows]

@@ -222,16 +222,21 @@ int hhsr_ref_planes(const float* guide_means, const float* guide_vars, int lh, i
                     uint32_t* curve_index, void* stream);
 /* Fused warp-upsample of the frame's guide means + colour distance + noise-model shrink + threshold
  * (robustness.py:359-421, 453-461, 505-528, 627-639) -> R float32 [2lh][2lw].
- * ref_sigma_sq / ref_curve_index from hhsr_rob_sigma (index plane NULL = look the curve up per frame on
- * the slower generic kernel); diff_curve: device double[ncurve]. */
+ * ref_sigma_sq / ref_curve_index from hhsr_rob_sigma; diff_curve: device double[ncurve].
+ * Two kernels: with ts % 16 == 0, the packed curve indices and ncurve <= 1024 the fused float32 kernel of
+ * hhsr_rob_frames with one frame (|dR| <= 1e-4 against the reference's float64 chain); otherwise (index plane NULL,
+ * other tile sizes, longer curves) the slower generic kernel with the reference's float64 chain.  The fused kernel moves
+ * 16-byte vectors where W % 4 == 0 and ref_means / ref_sigma_sq / ref_curve_index / R are 16-byte aligned and dwords
+ * elsewhere: R does not depend on the alignment, bit for bit. */
 int hhsr_rob_frame(const float* comp_means, int lh, int lw, const float* ref_means, const float* ref_sigma_sq,
                    const uint32_t* ref_curve_index, const float* flow, int ny, int nx, int ts, const float* S,
                    const double* diff_curve, int ncurve, double t, float* R, void* stream);
 /* hhsr_rob_frame for n_frames frames of one burst (HOST arrays of device pointers): groups of 4 frames share one pass
  * over the reference-frame planes (20 of the 27 bytes per pixel and frame); per frame bit-identical to hhsr_rob_frame.
+ * Where the fused kernel does not apply (see hhsr_rob_frame) the generic kernel runs once per frame.
  * S = NULL: the per-tile weights of hhsr_rob_s are evaluated inside the kernel from (Mt, s1, s2) — one launch less per
- * frame; only with the grouped kernel (ts % 16 == 0, W % 4 == 0, packed curve indices, 16-byte aligned planes; error -3
- * otherwise).  With S given, Mt / s1 / s2 are ignored.  flow_rows_before / flow_rows_after: as in hhsr_rob_s, for the
+ * frame, the same bits as with the maps of hhsr_rob_s; only with the fused kernel (ts % 16 == 0, packed curve indices,
+ * ncurve <= 1024; error -3 otherwise).  With S given, Mt / s1 / s2 are ignored.  flow_rows_before / flow_rows_after: as in hhsr_rob_s, for the
  * weights evaluated inside the kernel (every flows[n] is a row slice with that many tile rows around it). */
 int hhsr_rob_frames(const float* const* comp_means, int n_frames, int lh, int lw, const float* ref_means,
                     const float* ref_sigma_sq, const uint32_t* ref_curve_index, const float* const* flows, int ny,
@@ -265,7 +270,7 @@ int hhsr_rob_sum(const float* const* rs, int n_frames, int H, int W, int flags, 
  *   flow NULL = the reference frame.
  * hhsr_mono_rob_sigma / hhsr_mono_rob_frame: robustness.py:505-528 / the fused per-frame pass -> R, one channel.
  *   hhsr_mono_rob_frame: with W % 4 == 0, ts % 4 == 0 and 16-byte aligned ref_means / sigma_sq / R the float32
- *   4-pixels-per-thread kernel runs (|dR| <= 1e-4 like the Bayer kernels), otherwise the float64 one-pixel kernel. */
+ *   4-pixels-per-thread kernel runs (|dR| <= 1e-4 like the fused Bayer kernel), otherwise the float64 one-pixel kernel. */
 int hhsr_mono_frame_stats(const float* raw, int H, int W, int pitch, float* means, float* vars, float* covs,
                           double alpha, double beta, double k_detail, double k_denoise, double D_th, double D_tr,
                           double k_stretch, double k_shrink, int law, void* stream);

@@ -21,7 +21,7 @@ pointers: they get the layouts they accept.
 
 The second half applies the guard bands to the entry points without a pitch that write whole planes from grids with
 remainder tiles, and reaches the kernels that the dispatchers only pick for outputs that are NOT 16-byte aligned (the
-first-generation x2 merge, the tile merge at x3, k_rob_frame_tile) or without a packed curve index (k_rob_frame): a C
+first-generation x2 merge, the tile merge at x3, the dword k_rob_frames_row4) or without a packed curve index (k_rob_frame): a C
 client produces those with one pointer offset."""
 import numpy as np
 import pytest
@@ -1058,16 +1058,16 @@ def _plane_ops():
         fn.__name__ = name
         op(fn)
 
-    rob("hhsr_rob_frames k_rob_frames_row4", 200, 328, 16, True)
-    rob("hhsr_rob_frame k_rob_frame_row4", 200, 328, 16, False)
-    rob("hhsr_rob_frame k_rob_frame_tile", 200, 330, 32, False)
+    rob("hhsr_rob_frames row4", 200, 328, 16, True)
+    rob("hhsr_rob_frame row4", 200, 328, 16, False)
+    rob("hhsr_rob_frame row4 W%4=2", 200, 330, 32, False)
     rob("hhsr_rob_frame k_rob_frame", 200, 330, 8, False)
     return ops
 
 
 PLANE_OPS = ["hhsr_rob_upscale", "hhsr_ref_planes", "hhsr_local_min5", "hhsr_rob_sum", "hhsr_flow_upscale_nearest",
-             "hhsr_frame_count_denoise", "hhsr_postprocess", "hhsr_orient_plane", "hhsr_rob_frames k_rob_frames_row4",
-             "hhsr_rob_frame k_rob_frame_row4", "hhsr_rob_frame k_rob_frame_tile", "hhsr_rob_frame k_rob_frame"]
+             "hhsr_frame_count_denoise", "hhsr_postprocess", "hhsr_orient_plane", "hhsr_rob_frames row4",
+             "hhsr_rob_frame row4", "hhsr_rob_frame row4 W%4=2", "hhsr_rob_frame k_rob_frame"]
 _OPS = {}
 
 
@@ -1106,8 +1106,9 @@ def test_merge_burst_output_off_the_16_byte_grid(scale, flags):
 
 def test_misaligned_outputs_refused_where_no_other_kernel_applies():
     """HHSR_MERGE_LOCAL_MIN at x3 and hhsr_merge_burst_chain need the wave-per-class kernels: on an output off the 16-byte
-    grid they return -3 with their documented text instead of launching; so does hhsr_rob_frames with S = NULL and a
-    misaligned R."""
+    grid they return -3 with their documented text instead of launching.  hhsr_rob_frames with S = NULL is refused where
+    k_rob_frame is the only kernel (no packed curve index); on a misaligned R it runs (the dword k_rob_frames_row4 evaluates
+    the weights itself) and gives the bits of the aligned call with the maps of hhsr_rob_s."""
     lib = _lib.load()
     c = Call("x3 local min, misaligned")
     rc = lib.hhsr_merge_burst(*_merge_burst(c, 3, "rggb", 0, DO_REF | DIVIDE | LOCAL_MIN, "compact", num_lead=1))
@@ -1123,13 +1124,20 @@ def test_misaligned_outputs_refused_where_no_other_kernel_applies():
                                     _lib.ptr(num), None, None, sH, sW, _lib.ptr(cls), 0, _lib.stream())
     assert rc == -3 and b"needs the wave-per-class x2 kernel" in lib.hhsr_last_error(), lib.hhsr_last_error()
     c.done()
-    _, rc, err, _ = _rob_frames_call(Call("rob_frames S = NULL, misaligned R"), grouped=True, lead=1, s_null=True)
-    assert rc == -3, (rc, err)
+    _, rc, err, _ = _rob_frames_call(Call("rob_frames S = NULL, no curve index"), grouped=True, lead=0, index=False, s_null=True)
+    assert rc == -3 and b"S = NULL" in err and b"needs the grouped kernel" in err, (rc, err)
+    got, rc, err, _ = _rob_frames_call(Call("rob_frames S = NULL, misaligned R"), grouped=True, lead=1, s_null=True)
+    assert rc == 0, (rc, err)
+    aligned, rc, err, want = _rob_frames_call(Call("rob_frames S given, aligned R"), grouped=True, lead=0)
+    assert rc == 0 and aligned.keys() == got.keys() and len(got) == len(want), (rc, err)
+    for k in got:
+        same_bits(got[k], aligned[k], f"hhsr_rob_frames {k}: S = NULL on a misaligned R vs S given on an aligned R")
 
 
 def _rob_frames_call(c, grouped, lead, index=True, s_null=False):
-    """hhsr_rob_frames (grouped) / hhsr_rob_frame on the k_rob_frames_row4 shape (ts % 16 == 0, W % 4 == 0) with R `lead`
-    elements off the 16-byte grid and with or without the packed curve index: (results or None, return code, message)."""
+    """hhsr_rob_frames (grouped) / hhsr_rob_frame on the shape of the 16-byte k_rob_frames_row4 (ts % 16 == 0, W % 4 == 0)
+    with R `lead` elements off the 16-byte grid, with or without the packed curve index and the maps S: (results, return
+    code, message, the oracle's maps)."""
     H, W, ts = 200, 328, 16
     lib = _lib.load()
     cfg, comp, flows, want, rm, rv, curves, (sig2, idx), cms = _rob_inputs(H, W, ts, 40 + ts)
@@ -1155,14 +1163,20 @@ def _rob_frames_call(c, grouped, lead, index=True, s_null=False):
 
 
 @pytest.mark.parametrize("grouped", [False, True], ids=["hhsr_rob_frame", "hhsr_rob_frames"])
-@pytest.mark.parametrize("route", ["k_rob_frame_tile", "k_rob_frame"])
+@pytest.mark.parametrize("route", ["k_rob_frames_row4_dword", "k_rob_frame"])
 def test_rob_frame_kernels_chosen_by_pointer(route, grouped):
-    """On the shape of k_rob_frames_row4: with R off the 16-byte grid k_rob_frame_tile runs, without a packed curve index
-    k_rob_frame; hhsr_rob_frame and hhsr_rob_frames (S given), against oracle.compute_robustness at the 1e-4 of
-    test_variant_parity.py::test_robustness_kernels_vs_oracle, guards intact."""
-    lead, index = (1, True) if route == "k_rob_frame_tile" else (0, False)
+    """On the shape of the 16-byte k_rob_frames_row4: with R off the 16-byte grid its dword instantiation runs, without a
+    packed curve index k_rob_frame; hhsr_rob_frame and hhsr_rob_frames (S given), against oracle.compute_robustness at the
+    1e-4 of test_variant_parity.py::test_robustness_kernels_vs_oracle, guards intact.  R does not depend on the alignment:
+    the misaligned call gives the bits of the same call on an aligned R."""
+    lead, index = (1, True) if route == "k_rob_frames_row4_dword" else (0, False)
     got, rc, err, want = _rob_frames_call(Call(route), grouped, lead, index)
     assert rc == 0, (rc, err)
+    if lead:
+        aligned, rc, err, _ = _rob_frames_call(Call(route + ", aligned R"), grouped, 0, index)
+        assert rc == 0 and aligned.keys() == got.keys() and len(got) == len(want), (rc, err)
+        for k in got:
+            same_bits(got[k], aligned[k], f"{route} {k}: R one element off the 16-byte grid vs aligned")
     for k, w in enumerate(want):  # (the oracle's map is r = the 5 x 5 minimum of the thresholded map R the kernels write)
         close(oracle.robustness.local_min(got[f"R{k}"]), w, 0, 1e-4,
               f"{route} ({'hhsr_rob_frames' if grouped else 'hhsr_rob_frame'}) frame {k}")

@@ -8,7 +8,7 @@ the oracle on identical inputs, on grids that give the XCD-aware workgroup remap
   alignment    every k_align_wave<ts, r, L1> instantiation through hhsr_align_level_batch (a partial second batch, the
                coarser level's flow read in place) and the ts = 64 block-matching + ICA kernels
   grey         the rocFFT fallback plans (plain, pruned, transposed) at sensor sizes with prime factors 17 / 19 / 31
-  robustness   k_rob_frames_row4, k_rob_frame_tile and k_rob_frame
+  robustness   k_rob_frames_row4<VEC> (16-byte and dword instantiation) and k_rob_frame; the entry points against each other
 
 Tolerances are the ones of tests/test_hip_parity.py for the same stages (merge rtol 2e-5 / atol 1e-6, flows 2e-4 px
 with the block-matching near-tie rule, grey 3e-6, robustness 1e-4)."""
@@ -449,7 +449,18 @@ def test_grey_library_plans_at_non_smooth_sizes(shape, monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------ robustness
+_ROB_CASES = {}
+
+
 def _rob_case(H, W, ts, seed):
+    """One robustness case with its oracle maps, built once per (H, W, ts, seed) and left unchanged by its users."""
+    key = (H, W, ts, seed)
+    if key not in _ROB_CASES:
+        _ROB_CASES[key] = _make_rob_case(H, W, ts, seed)
+    return _ROB_CASES[key]
+
+
+def _make_rob_case(H, W, ts, seed):
     wb = [1.8, 1.0, 1.4]
     cfa = [[1, 0], [2, 1]]
     ref, comp, _ = synth.make_burst(H, W, 3, seed=seed, wb=wb, occluder=True, max_shift=1.5, cfa=((1, 0), (2, 1)))
@@ -464,22 +475,24 @@ def _rob_case(H, W, ts, seed):
     return cfg, cfa, wb, comp, flows, want, rm, rv, curves
 
 
-@pytest.mark.parametrize("H,W,ts,kernel", [(200, 328, 16, "k_rob_frames_row4"), (200, 330, 32, "k_rob_frame_tile"),
+@pytest.mark.parametrize("H,W,ts,kernel", [(200, 328, 16, "k_rob_frames_row4"), (200, 330, 32, "k_rob_frames_row4_dword"),
                                             (200, 330, 8, "k_rob_frame")])
 def test_robustness_kernels_vs_oracle(H, W, ts, kernel):
-    """hhsr_rob_frame / hhsr_rob_frames choose k_rob_frame_row4 / k_rob_frames_row4 (ts % 16 == 0, W % 4 == 0),
-    k_rob_frame_tile (ts % 16 == 0, W = 2 mod 4) and k_rob_frame (everything else); each against oracle.compute_robustness
-    on a grid with nblk % 8 != 0 (32 x 32-pixel workgroups: 11 x 7 = 77; k_rob_frame's 64 x 4: 6 x 50 = 300).  k_rob_frame is
-    reached through ts = 8.  A noise curve of more than 1024 entries is not an input the Python API accepts (the curves have
-    1001 entries); the other routes to it and to k_rob_frame_tile (no packed curve index, planes that are not 16-byte
-    aligned) are not inputs the Python API produces (torch allocations are aligned), but a C client produces them with one
-    pointer offset: tests/test_pitched_buffers.py::test_rob_frame_kernels_chosen_by_pointer reaches them through the C ABI."""
+    """hhsr_rob_frame (one frame) and hhsr_rob_frames choose k_rob_frames_row4<VEC> where ts % 16 == 0 — its 16-byte
+    instantiation with W % 4 == 0, the dword one with W = 2 mod 4 — and k_rob_frame everywhere else; each against
+    oracle.compute_robustness on a grid with nblk % 8 != 0 (32 x 32-pixel workgroups: 11 x 7 = 77; k_rob_frame's 64 x 4:
+    6 x 50 = 300).  k_rob_frame is reached through ts = 8.  A noise curve of more than 1024 entries is not an input the
+    Python API accepts (the curves have 1001 entries); the other route to it (no packed curve index) and the other route to
+    the dword instantiation (planes that are not 16-byte aligned) are not inputs the Python API produces (torch allocations
+    are aligned), but a C client produces them with one pointer offset:
+    tests/test_pitched_buffers.py::test_rob_frame_kernels_chosen_by_pointer reaches them through the C ABI."""
     cfg, cfa, wb, comp, flows, want, rm, rv, curves = _rob_case(H, W, ts, 40 + ts)
-    assert (ts % 16 == 0) == (kernel != "k_rob_frame") and (W % 4 == 0) == (kernel == "k_rob_frames_row4")
+    assert (ts % 16 == 0) == kernel.startswith("k_rob_frames_row4")
+    assert (ts % 16 == 0 and W % 4 != 0) == kernel.endswith("_dword")
     for k, (c, f) in enumerate(zip(comp, flows)):
         r = robustness.compute_robustness(T(c), rm, rv, T(f), cfa, wb, curves, cfg)
         assert_close(N(r), want[k], 0, 1e-4, f"{kernel} (compute_robustness) frame {k}")
-    if ts % 16 == 0:  # the grouped entry point: k_rob_frames_row4, or per-frame k_rob_frame_tile when W % 4 != 0
+    if ts % 16 == 0:  # the grouped entry point, the weights S evaluated inside the kernel in either instantiation
         sig = robustness.noise_sigma_sq(rm, rv, curves[0])
         cms = [robustness.compute_local_stats_from_raw(T(c), cfa, wb, want_vars=False)[0] for c in comp]
         rs = robustness.compute_robustness_group([T(c) for c in comp], rm, [T(f) for f in flows], curves, cfg, sig, cms)
@@ -487,3 +500,48 @@ def test_robustness_kernels_vs_oracle(H, W, ts, kernel):
             assert_close(N(r), want[k], 0, 1e-4, f"{kernel} (compute_robustness_group) frame {k}")
     lo = np.mean([(w < 0.5).mean() for w in want])
     assert 0.01 < lo < 0.9, f"inputs do not exercise the robustness ({lo})"
+
+
+def _bits(a):
+    return N(a).view(np.int32)
+
+
+def test_robustness_entry_points_same_bits():
+    """The two promises of include/hhsr.h on the vector route (200 x 328, ts = 16, aligned planes), as equal bits and not
+    as a tolerance: hhsr_rob_frames with S given is per frame hhsr_rob_frame, and hhsr_rob_frames with S = NULL (the
+    weights evaluated inside the kernel) is hhsr_rob_frames with the maps of hhsr_rob_s."""
+    H, W, ts = 200, 328, 16
+    cfg, cfa, wb, comp, flows, want, rm, rv, curves = _rob_case(H, W, ts, 56)
+    sig2, idx = robustness.noise_sigma_sq(rm, rv, curves[0])
+    assert idx is not None
+    cms = [robustness.compute_local_stats_from_raw(T(c), cfa, wb, want_vars=False)[0] for c in comp]
+    tf = [T(f) for f in flows]
+    ny, nx = flows[0].shape[:2]
+    t = cfg.robustness.tuning
+    S = [robustness.compute_s(f, t.Mt, t.s1, t.s2) for f in tf]
+    dif = curves[1]
+
+    def planes():
+        return [torch.full((H, W), float("nan"), dtype=torch.float32, device=DEV) for _ in comp]
+
+    def frames(maps):
+        Rs = planes()
+        _lib.call("hhsr_rob_frames", _lib.ptr_array(cms), len(cms), H // 2, W // 2, _lib.ptr(rm), _lib.ptr(sig2),
+                  _lib.ptr(idx), _lib.ptr_array(tf), ny, nx, ts, None if maps is None else _lib.ptr_array(maps), float(t.Mt),
+                  float(t.s1), float(t.s2), _lib.ptr(dif), dif.numel(), float(t.t), _lib.ptr_array(Rs), 0, 0, _lib.stream())
+        return Rs
+
+    single = planes()
+    for k in range(len(cms)):
+        _lib.call("hhsr_rob_frame", _lib.ptr(cms[k]), H // 2, W // 2, _lib.ptr(rm), _lib.ptr(sig2), _lib.ptr(idx),
+                  _lib.ptr(tf[k]), ny, nx, ts, _lib.ptr(S[k]), _lib.ptr(dif), dif.numel(), float(t.t), _lib.ptr(single[k]),
+                  _lib.stream())
+    given, inline = frames(S), frames(None)
+    torch.cuda.synchronize()
+    for k in range(len(cms)):
+        assert not np.isnan(N(given[k])).any(), f"frame {k}: pixels left unwritten"
+        d = np.abs(N(single[k]) - N(given[k])).max()
+        print(f"frame {k}: hhsr_rob_frame vs hhsr_rob_frames max |dR| {d:.3g}; "
+              f"S given vs S = NULL max |dR| {np.abs(N(given[k]) - N(inline[k])).max():.3g}")
+        assert np.array_equal(_bits(single[k]), _bits(given[k])), f"frame {k}: hhsr_rob_frame != hhsr_rob_frames ({d})"
+        assert np.array_equal(_bits(given[k]), _bits(inline[k])), f"frame {k}: S given != S = NULL"
