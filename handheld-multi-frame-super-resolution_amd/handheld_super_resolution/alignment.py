@@ -9,16 +9,14 @@ from . import _lib
 from .config import hip_opt
 from .ICA import init_ica, align_lvl_ica
 from .block_matching import align_lvl_block_matching_L2, align_lvl_block_matching_L1
-from .utils_image import cuda_downsample, cuda_downsample_batch
+from .utils_image import cuda_downsample_batch
 
 
 def build_gaussian_pyramid(image, factors=[1, 2, 4, 4], kernel="gaussian"):
     """alignment.py:74-82: compact contiguous levels, coarse first."""
-    pyramid = [cuda_downsample(image, kernel, factors[0])]
-    for factor in factors[1:]:
-        pyramid.append(cuda_downsample(pyramid[-1], kernel, factor))
-    pyramid = [lvl.reshape(lvl.shape[-2:]) for lvl in pyramid]
-    return pyramid[::-1]
+    if kernel != "gaussian":
+        raise ValueError("please use gaussian kernel")
+    return build_gaussian_pyramids([image.reshape(image.shape[-2:])], factors)[0]
 
 
 def build_gaussian_pyramids(images, factors=[1, 2, 4, 4]):
@@ -95,34 +93,37 @@ def _fused_level(l, config):
     return None
 
 
+def _align_level_fused(fl, ref_lvl, ref_hessian_lvl, movs, flows, coarse, config):
+    """ONE launch of the fused block-matching + ICA kernel for a list of frames (hhsr_align_level_batch).  `coarse`: where
+    the incoming flows come from instead of `flows` — None (in place), "zero" or (coarser flows, rep, mult) for the
+    nearest-neighbour upscaling of upscale_lvl() fused into the launch; `flows` then only receive the result."""
+    code, ts, r = fl
+    ny, nx, _ = flows[0].shape
+    mh, mw = movs[0].shape
+    rh, rw = ref_lvl.shape
+    assert ref_lvl.is_contiguous() and all(t.is_contiguous() for t in (*movs, *flows))
+    if coarse is None:
+        cptr, cny, cnx, rep, mult = None, 0, 0, 0, 1.0
+    elif isinstance(coarse, str):
+        cptr, cny, cnx, rep, mult = None, 0, 0, -1, 1.0
+    else:
+        cfs, rep, mult = coarse
+        assert all(cf.is_contiguous() and cf.dtype == torch.float32 for cf in cfs)
+        cptr, (cny, cnx) = _lib.ptr_array(cfs), cfs[0].shape[:2]
+    _lib.call("hhsr_align_level_batch", _lib.ptr(ref_lvl), rh, rw, rw, _lib.ptr(ref_hessian_lvl), _lib.ptr_array(movs),
+              len(movs), mh, mw, mw, _lib.ptr_array(flows), ny, nx, ts, r, code, int(config.ica.tuning.n_iter), cptr,
+              int(cny), int(cnx), int(rep), float(mult), _lib.stream())
+
+
 def align_lvl(ref_lvl, tyled_pyr_lvl, ref_fft_lvl, ref_gradx_lvl, ref_grady_lvl, ref_hessian_lvl, moving_lvl,
-              alignments, l, config, coarse=None):
-    """Block matching then ICA on one level (alignment.py:125-147).  For tiles up to 32 pixels both steps
-    run in ONE fused kernel (hhsr_align_level; config.hip.fused_align: false selects the two-kernel path,
-    which is also what 64-pixel tiles use).  `coarse` (fused kernel only): where the incoming flow comes from
-    instead of `alignments` — "zero" or (coarser_flow, rep, mult) for the nearest-neighbour upscaling of
-    upscale_lvl() fused into the launch; `alignments` then only receives the result."""
+              alignments, l, config):
+    """Block matching then ICA on one level, in place on `alignments` (alignment.py:125-147).  For tiles up to 32 pixels
+    both steps run in ONE fused kernel (config.hip.fused_align: false selects the two-kernel path, which is also what
+    64-pixel tiles use)."""
     metric = config.block_matching.tuning.metrics[l]
     fl = _fused_level(l, config)
     if fl is not None:
-        code, ts, r = fl
-        ny, nx, _ = alignments.shape
-        mh, mw = moving_lvl.shape
-        rh, rw = ref_lvl.shape
-        assert ref_lvl.is_contiguous() and moving_lvl.is_contiguous() and alignments.is_contiguous()
-        if coarse is None:
-            cptr, cny, cnx, rep, mult = None, 0, 0, 0, 1.0
-        elif isinstance(coarse, str):
-            cptr, cny, cnx, rep, mult = None, 0, 0, -1, 1.0
-        else:
-            cf, rep, mult = coarse
-            assert cf.is_contiguous() and cf.dtype == torch.float32
-            cptr, (cny, cnx) = cf, cf.shape[:2]
-        _lib.call("hhsr_align_level", _lib.ptr(ref_lvl), rh, rw, rw, _lib.ptr(ref_hessian_lvl), _lib.ptr(moving_lvl),
-                  mh, mw, mw, _lib.ptr(alignments), ny, nx, ts, r, code, int(config.ica.tuning.n_iter),
-                  _lib.ptr(cptr), int(cny), int(cnx), int(rep), float(mult), _lib.stream())
-        return
-    assert coarse is None, "fused flow upscaling needs the fused level kernel"
+        return _align_level_fused(fl, ref_lvl, ref_hessian_lvl, [moving_lvl], [alignments], None, config)
     if metric == "L2":
         align_lvl_block_matching_L2(ref_lvl, ref_fft_lvl, moving_lvl, alignments, l, config)
     elif metric == "L1":
@@ -136,82 +137,58 @@ def align_lvl(ref_lvl, tyled_pyr_lvl, ref_fft_lvl, ref_gradx_lvl, ref_grady_lvl,
 
 def align(ref_pyramid, tyled_pyr, ref_tiled_fft, ref_gradx, ref_grady, ref_hessian, img, config,
           moving_pyramid=None):
-    """Coarse-to-fine alignment of one grey frame (alignment.py:84-123).  Everything is enqueued on
-    torch's current stream: no host synchronisation between levels (the reference needs a
-    cuda.synchronize() per level to order its torch and Numba streams).  `moving_pyramid`: the frame's
-    pyramid when the caller already built it (it does not depend on the reference frame)."""
-    img = _lib.f32c(img)
-    factors = config.block_matching.tuning.factors
+    """Coarse-to-fine alignment of one grey frame (alignment.py:84-123): align_batch() of one pyramid.  `moving_pyramid`:
+    the frame's pyramid when the caller already built it (it does not depend on the reference frame)."""
     if moving_pyramid is None:
-        moving_pyramid = build_gaussian_pyramid(img, factors)
-    alignments = None
-    n = len(ref_pyramid)
-    for i in range(n):
-        l = n - i - 1
-        ts = config.block_matching.tuning.tile_sizes[l]
-        grid = (ref_pyramid[i].shape[0] // ts, ref_pyramid[i].shape[1] // ts)
-        bm = config.block_matching.tuning
-        coarse = None
-        q = bm.tile_sizes[l] // bm.tile_sizes[l + 1] if alignments is not None else 1
-        rep = bm.factors[l + 1] // q if (alignments is not None and q > 0) else 1
-        if (_fused_level(l, config) is not None and rep > 0 and
-                (alignments is None or bm.flow_upscale_mode == "nearest")):
-            # the level kernel takes its incoming flow straight from the coarser level (or zero): no separate
-            # upscaling / memset launch
-            if alignments is None:
-                coarse = "zero"
-            else:
-                coarse = (alignments, rep, float(bm.factors[l + 1]))
-            alignments = torch.empty((*grid, 2), dtype=torch.float32, device=img.device)
-        elif alignments is None:
-            alignments = torch.zeros((*grid, 2), dtype=torch.float32, device=img.device)
-        else:
-            alignments = upscale_lvl(alignments, grid, l, config)
-        align_lvl(ref_pyramid[i], tyled_pyr[i], ref_tiled_fft[i], ref_gradx[i], ref_grady[i], ref_hessian[i],
-                  moving_pyramid[i], alignments, l, config, coarse=coarse)
-    return alignments
+        moving_pyramid = build_gaussian_pyramid(_lib.f32c(img), config.block_matching.tuning.factors)
+    return align_batch(ref_pyramid, ref_hessian, [moving_pyramid], config, ref_gradx, ref_grady)[0]
+
+
+def _reads_coarse(l, config):
+    """rep > 0 when level l's fused kernel can take its incoming flow straight from the coarser level (nearest-neighbour
+    upscaling by `rep` fused into the launch: no separate upscaling launch), else 0.  Not for the coarsest level."""
+    bm = config.block_matching.tuning
+    q = bm.tile_sizes[l] // bm.tile_sizes[l + 1]
+    if _fused_level(l, config) is None or q <= 0 or bm.flow_upscale_mode != "nearest":
+        return 0
+    return max(bm.factors[l + 1] // q, 0)
 
 
 def can_align_batch(config):
-    """Every level runs on the fused level kernel with the coarser flow read in place (see align())."""
-    bm = config.block_matching.tuning
-    n = len(bm.factors)
-    for l in range(n):
-        if _fused_level(l, config) is None:
-            return False
-        if l + 1 < n:
-            q = bm.tile_sizes[l] // bm.tile_sizes[l + 1]
-            if q <= 0 or bm.factors[l + 1] // q <= 0 or bm.flow_upscale_mode != "nearest":
-                return False
-    return True
+    """Every level runs on the fused level kernel with the coarser flow read in place: align_batch() is then one launch
+    per level for any number of frames."""
+    n = len(config.block_matching.tuning.factors)
+    return _fused_level(n - 1, config) is not None and all(_reads_coarse(l, config) > 0 for l in range(n - 1))
 
 
-def align_batch(ref_pyramid, ref_hessian, moving_pyramids, config):
-    """align() of several frames against one reference pyramid: ONE launch per level for the whole chunk
-    (hhsr_align_level_batch) — the coarse levels are 7-27 us launches of a few hundred workgroups that cannot fill the
-    GPU one frame at a time.  Needs can_align_batch(config); per frame bit-identical to align().
-    Returns the list of finest-level flow fields (views of one [n, ny, nx, 2] tensor)."""
+def align_batch(ref_pyramid, ref_hessian, moving_pyramids, config, ref_gradx=None, ref_grady=None):
+    """Coarse-to-fine alignment of several frames against one reference pyramid; everything is enqueued on torch's current
+    stream, no host synchronisation between levels (the reference needs a cuda.synchronize() per level to order its torch
+    and Numba streams).  A level that runs on the fused kernel with the coarser flow read in place (or zero) is ONE launch
+    for all frames (hhsr_align_level_batch) — the coarse levels are 7-27 us launches of a few hundred workgroups that
+    cannot fill the GPU one frame at a time; with can_align_batch(config) that is every level.  Any other level runs frame
+    by frame: upscale_lvl() or zeros, then align_lvl() (which needs `ref_gradx` / `ref_grady` for its two-kernel path).
+    Returns the list of finest-level flow fields."""
     bm = config.block_matching.tuning
     n_lvl, nf = len(ref_pyramid), len(moving_pyramids)
     dev = moving_pyramids[0][0].device
     prev = None
     for i in range(n_lvl):
         l = n_lvl - i - 1
-        code, ts, r = _fused_level(l, config)
-        ref_lvl = ref_pyramid[i]
-        rh, rw = ref_lvl.shape
-        ny, nx = rh // ts, rw // ts
+        ts = bm.tile_sizes[l]
+        ny, nx = ref_pyramid[i].shape[0] // ts, ref_pyramid[i].shape[1] // ts
         movs = [p[i] for p in moving_pyramids]
-        mh, mw = movs[0].shape
-        flows = list(torch.empty((nf, ny, nx, 2), dtype=torch.float32, device=dev).unbind(0))
-        if prev is None:
-            cptr, cny, cnx, rep, mult = None, 0, 0, -1, 1.0
+        fl = _fused_level(l, config)
+        rep = _reads_coarse(l, config) if prev is not None else 0
+        if fl is not None and (prev is None or rep > 0):
+            flows = list(torch.empty((nf, ny, nx, 2), dtype=torch.float32, device=dev).unbind(0))
+            coarse = "zero" if prev is None else (prev, rep, float(bm.factors[l + 1]))
+            _align_level_fused(fl, ref_pyramid[i], ref_hessian[i], movs, flows, coarse, config)
         else:
-            q = bm.tile_sizes[l] // bm.tile_sizes[l + 1]
-            rep, mult = bm.factors[l + 1] // q, float(bm.factors[l + 1])
-            cptr, (cny, cnx) = _lib.ptr_array(prev), prev[0].shape[:2]
-        _lib.call("hhsr_align_level_batch", _lib.ptr(ref_lvl), rh, rw, rw, _lib.ptr(ref_hessian[i]), _lib.ptr_array(movs),
-                  nf, mh, mw, mw, _lib.ptr_array(flows), ny, nx, ts, r, code, int(config.ica.tuning.n_iter), cptr,
-                  int(cny), int(cnx), int(rep), float(mult), _lib.stream())
+            flows = []
+            for k, mov in enumerate(movs):
+                flows.append(torch.zeros((ny, nx, 2), dtype=torch.float32, device=dev) if prev is None
+                             else upscale_lvl(prev[k], (ny, nx), l, config))
+                align_lvl(ref_pyramid[i], None, None, ref_gradx[i], ref_grady[i], ref_hessian[i], mov, flows[k], l, config)
         prev = flows
     return prev

@@ -335,17 +335,16 @@ class HostBurstRunner:
                     i0 += int(k)
             st.streams = [pool[c % ns] for c in range(len(st.chunks))]  # (FFT plans exist per pool stream: eager call)
             if cfg.grey_method == "FFT":  # plans allocate: they have to exist before their stream is captured
-                from . import _lib
-                from .utils_image import _grey_plan
+                from .utils_image import _grey_plan, plan_batch
 
                 for idx, s in zip(st.chunks, st.streams):
                     with torch.cuda.stream(s):
-                        _grey_plan(H, W, dev, _lib.MAX_BATCH if len(idx) > 1 else 1)
+                        _grey_plan(H, W, dev, plan_batch(len(idx)))
             st.g_chunks, results = [], []
             for idx, s in zip(st.chunks, st.streams):
                 g = torch.cuda.CUDAGraph()
                 with capture(g, s):
-                    fronts = pipe._front_chunk([staged[1 + i] for i in idx], None, idx, None)
+                    fronts = pipe._grouped(staged[1:], None, idx, pipe._inject_flows)
                     results.append(pipe._robustness(fronts, None, fuse_min))
                 st.g_chunks.append(g)
             st.frames = [f for chunk in results for f in chunk]

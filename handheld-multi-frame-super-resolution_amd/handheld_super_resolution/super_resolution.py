@@ -26,8 +26,7 @@ from . import _lib
 from .config import hip_opt
 from .utils_image import compute_grey_images, compute_grey_images_batch
 from .utils import divide, add, getTime, timer
-from .alignment import (align, init_alignment, build_gaussian_pyramid, build_gaussian_pyramids, align_batch,
-                        can_align_batch)
+from .alignment import init_alignment, build_gaussian_pyramids, align_batch, can_align_batch
 from .params import sanitize_config, update_snr_config
 from .robustness import (init_robustness, compute_robustness, compute_robustness_group, noise_curves_to_device, RobustnessSum,
                          ref_planes, upscale_warp_stats, mono_sigma_sq)
@@ -75,6 +74,15 @@ def _device():
 
 
 ROB_GROUP = 4  # frames per robustness launch (hhsr_rob_frames)
+
+
+def front_groups(k, batch, given, robustness, mono, batchable):
+    """Sizes of the launch groups the front end runs for a chunk of k frames, `given` of which come with a flow field.
+    The whole chunk is ONE group (one launch per stage) when the batched front end is on (BurstPipeline._batch) and either
+    every flow is given — no alignment, one raw pass, which only the Bayer robustness path has in list form — or none is
+    and every alignment level takes a list of frames (`batchable`: alignment.can_align_batch); else k groups of one."""
+    whole = k >= 2 and batch and ((given == k and robustness and not mono) or (given == 0 and batchable))
+    return [k] if whole else [1] * k
 
 
 def _tensors(x):
@@ -130,8 +138,6 @@ class BurstPipeline:
         self._inject_flows = hip_opt(config, "inject_flows")
         # frames given as integer sensor counts: {"black_levels": [R, G, B], "white_level": w} (see _ingest)
         self._raw_norm = hip_opt(config, "raw_norm")
-        # chunk-batched front end (one launch per stage for a chunk of frames, see _front_chunk); config.hip.batch: false
-        # keeps the per-frame launches (A/B, tests)
         # (before, after): the flow fields handed to this pipeline are row slices (views) of larger fields with that many
         # tile rows around them — the sub-image pipelines of distributed.py; see robustness.compute_s
         self.flow_rows = (0, 0)
@@ -139,6 +145,8 @@ class BurstPipeline:
         # before the frames itself (distributed.RowsPlan captures them as separate graphs: an event recorded in one
         # capture cannot be waited for in another)
         self.ref_wait = True
+        # chunk-batched front end (one launch per stage for a chunk of frames, see front_groups); config.hip.batch: false
+        # keeps the per-frame launches (A/B, tests), and so do the per-frame timers and the grey methods without a list form
         self._batch = bool(hip_opt(config, "batch")) and (self.mono or self.grey_method == "FFT") and config.verbose < 2
 
     def _ingest(self, img):
@@ -261,91 +269,58 @@ class BurstPipeline:
         ts = int(self.config.block_matching.tuning.tile_size)
         return lvl0.shape[0] // ts, lvl0.shape[1] // ts
 
-    def align_frame(self, img, wait_ref=None):
-        """grey -> pyramid -> coarse-to-fine alignment of one comp frame: flow float32 [ny, nx, 2]."""
-        cfg = self.config
-        raw = self._ingest(img)
-        grey = raw if self.mono else compute_grey_images(raw, self.grey_method)
-        pyramid = build_gaussian_pyramid(grey, cfg.block_matching.tuning.factors)
-        if wait_ref is not None:
-            torch.cuda.current_stream(self.device).wait_event(self._align_ready)
-        return align(*self.align_state, grey, cfg, moving_pyramid=pyramid)
-
-    def _align_chunk(self, imgs, wait_ref=None):
-        """align_frame() of a chunk of frames with ONE launch per stage (grey transform phases, pyramid levels,
-        alignment levels) when the configuration allows it; per frame bit-identical to align_frame()."""
-        cfg = self.config
-        if len(imgs) < 2 or not self._batch or not can_align_batch(cfg):
-            return [self.align_frame(img, wait_ref) for img in imgs]
-        raws = [self._ingest(img) for img in imgs]
-        greys = raws if self.mono else compute_grey_images_batch(raws, self.grey_method)
-        pyramids = build_gaussian_pyramids(greys, cfg.block_matching.tuning.factors)
-        if wait_ref is not None:
-            torch.cuda.current_stream(self.device).wait_event(self._align_ready)
-        return align_batch(self.align_state[0], self.align_state[5], pyramids, cfg)
-
     def align_frames(self, comp_imgs, n_streams=None):
-        """align_frame() over a list of frames: chunks of frames round-robin on the side streams (like process_frames)."""
+        """Flow fields float32 [ny, nx, 2] of a list of frames (grey -> pyramid -> coarse-to-fine alignment): chunks of
+        frames round-robin on the side streams (like process_frames)."""
         with torch.cuda.device(self.device):
             comp_imgs = self.prefetch([comp_imgs[i] for i in range(len(comp_imgs))])
             chunks = self._chunks(len(comp_imgs), n_streams)
             out = self._on_streams(len(chunks), n_streams, False,
-                                   lambda ci, wait: self._align_chunk([comp_imgs[i] for i in chunks[ci]], wait_ref=wait))
+                                   lambda ci, wait: self._grouped(comp_imgs, wait, chunks[ci], None, stats=False))
             return [f for chunk in out for f in chunk]
 
-    def _front_chunk(self, imgs, wait_ref, indices, flows):
-        """_front() of a chunk of frames.  With the default configuration (Bayer frames, FFT grey image, fused level
-        kernels) every stage is ONE launch for the whole chunk — 3 transform phases, 3 pyramid levels, 4 alignment
-        levels, 1 raw pass: 11 launches per chunk instead of per frame — and the latency-bound stages (FFT phases,
-        coarse pyramid / alignment levels: a few hundred workgroups per frame) see enough work to fill the GPU.
-        Results per frame are bit-identical to _front() (tests: batch == single)."""
-        cfg = self.config
-        inj = [None if flows is None else flows[i] for i in indices]
-        if flows is None and self._inject_flows is not None:
-            inj = [self._inject_flows[i] for i in indices]
-        if len(imgs) >= 2 and self._batch and all(f is not None for f in inj) and cfg.robustness.enabled and not self.mono:
-            # every flow is given (multi-GPU step B on a row slab): no alignment, ONE raw pass for the chunk — on a slab
-            # a per-frame launch is a few hundred workgroups and leaves most of the GPU idle
-            raws = [self._ingest(img) for img in imgs]
-            stats = frame_stats_batch(raws, self.cfa, self.wb, cfg)
-            return [(raw, _lib.f32c(f, self.device), st[2], st[0]) for raw, f, st in zip(raws, inj, stats)]
-        if len(imgs) < 2 or not self._batch or not can_align_batch(cfg) or any(f is not None for f in inj):
-            return [self._front(img, wait_ref, i, f) for img, i, f in zip(imgs, indices, inj)]
-        raws = [self._ingest(img) for img in imgs]
-        greys = raws if self.mono else compute_grey_images_batch(raws, self.grey_method)  # mono: the frame itself
-        pyramids = build_gaussian_pyramids(greys, cfg.block_matching.tuning.factors)
-        if wait_ref is not None:
-            torch.cuda.current_stream(self.device).wait_event(self._align_ready)
-        fl = align_batch(self.align_state[0], self.align_state[5], pyramids, cfg)
-        if cfg.robustness.enabled:
-            stats = ([frame_stats(raw, self.cfa, self.wb, cfg) for raw in raws] if self.mono  # (per-pixel covariances)
-                     else frame_stats_batch(raws, self.cfa, self.wb, cfg))
-            return [(raw, f, st[2], st[0]) for raw, f, st in zip(raws, fl, stats)]
-        return [(raw, f, estimate_kernels(raw, cfg), None) for raw, f in zip(raws, fl)]
+    def _grouped(self, imgs, wait_ref, indices, flows, stats=True):
+        """_front_group() of the frames `indices` of a burst, in the launch groups of front_groups().  `flows`: flow fields
+        of the burst's frames that replace their alignment (None, or None for a frame: aligned here)."""
+        fl = [None if flows is None else flows[i] for i in indices]
+        groups = front_groups(len(indices), self._batch, sum(f is not None for f in fl), bool(self.config.robustness.enabled),
+                              self.mono, can_align_batch(self.config))
+        out, i0 = [], 0
+        for k in groups:
+            out += self._front_group([imgs[i] for i in indices[i0:i0 + k]], wait_ref, fl[i0:i0 + k], stats)
+            i0 += k
+        return out
 
-    def _front(self, img, wait_ref=None, index=None, flow=None):
-        """grey -> pyramid -> alignment -> guide means + kernel covariances of one comp frame:
-        (raw, flow, covs, guide means or None)."""
+    def _front_group(self, imgs, wait_ref, flows, stats=True):
+        """The front end of n >= 1 frames, one launch per stage: ingest, then grey -> pyramid -> alignment (or the given
+        `flows`: all or none), then guide means + kernel covariances.  Returns a list of (raw, flow, covs, guide means or
+        None), with `stats=False` of flows.  With the default configuration (Bayer frames, FFT grey image, fused level
+        kernels) that is 3 transform phases, 3 pyramid levels, 4 alignment levels, 1 raw pass: 11 launches per group instead
+        of per frame, and the latency-bound stages (FFT phases, coarse pyramid / alignment levels: a few hundred workgroups
+        per frame) see enough work to fill the GPU.  Results per frame do not depend on the grouping (tests: batch == single)."""
         cfg = self.config
-        raw = self._ingest(img)
-        if flow is None and self._inject_flows is not None and index is not None:
-            flow = self._inject_flows[index]
-        if flow is not None:
-            flow = _lib.f32c(flow, self.device)  # (nothing here needs the reference frame: the caller waits before the robustness)
+        raws = [self._ingest(img) for img in imgs]
+        if flows[0] is not None:  # (nothing here needs the reference frame: the caller waits before the robustness)
+            flows = [_lib.f32c(f, self.device) for f in flows]
         else:
-            grey = raw if self.mono else self._timed(
-                compute_grey_images, 3, end_s="- grey images estimated by {}".format(self.grey_method))(raw, self.grey_method)
-            pyramid = build_gaussian_pyramid(grey, cfg.block_matching.tuning.factors)
+            greys = raws if self.mono else self._timed(  # mono: the frame itself
+                compute_grey_images_batch, 3, end_s="- grey images estimated by {}".format(self.grey_method))(raws, self.grey_method)
+            pyramids = build_gaussian_pyramids(greys, cfg.block_matching.tuning.factors)
             if wait_ref is not None:
                 torch.cuda.current_stream(self.device).wait_event(self._align_ready)
-            flow = self._timed(align, 2, "\nBeginning alignment", "Image aligned (Total)")(
-                *self.align_state, grey, cfg, moving_pyramid=pyramid)
-        if cfg.robustness.enabled:  # guide means + kernel covariances from one pass over the raw frame
-            means, _, covs = self._timed(frame_stats, 2, "\nEstimating kernels + guide statistics",
-                                         "Kernels + guide statistics estimated (Total)")(raw, self.cfa, self.wb, cfg)
-        else:
-            means, covs = None, self._timed(estimate_kernels, 2, "\nEstimating kernels", "Kernels estimated (Total)")(raw, cfg)
-        return raw, flow, covs, means
+            st = self.align_state
+            flows = self._timed(align_batch, 2, "\nBeginning alignment", "Image aligned (Total)")(
+                st[0], st[5], pyramids, cfg, st[3], st[4])
+        if not stats:
+            return flows
+        if not cfg.robustness.enabled:
+            est = self._timed(estimate_kernels, 2, "\nEstimating kernels", "Kernels estimated (Total)")
+            return [(raw, f, est(raw, cfg), None) for raw, f in zip(raws, flows)]
+        # guide means + kernel covariances from one pass over the raw frames (mono: per-pixel covariances, frame by frame)
+        stat = self._timed(frame_stats if self.mono else frame_stats_batch, 2, "\nEstimating kernels + guide statistics",
+                           "Kernels + guide statistics estimated (Total)")
+        sts = [stat(raw, self.cfa, self.wb, cfg) for raw in raws] if self.mono else stat(raws, self.cfa, self.wb, cfg)
+        return [(raw, f, st[2], st[0]) for raw, f, st in zip(raws, flows, sts)]
 
     def _robustness(self, fronts, accumulate_r=None, fuse_local_min=False):
         """Robustness of a group of frames of the burst (one launch per 4 frames shares the pass over the
@@ -372,10 +347,12 @@ class BurstPipeline:
         (latency-bound) reference precompute.
         `flow`: a flow field that replaces the alignment (multi-GPU step B; validation hook
         config.hip.inject_flows via `index`)."""
-        front = self._front(img, wait_ref, index, flow)
+        if flow is None and self._inject_flows is not None and index is not None:
+            flow = self._inject_flows[index]
+        fronts = self._front_group([img], wait_ref, [flow])
         if wait_ref is not None:
             torch.cuda.current_stream(self.device).wait_event(wait_ref)
-        return self._robustness([front], accumulate_r, fuse_local_min)[0]
+        return self._robustness(fronts, accumulate_r, fuse_local_min)[0]
 
     def process_frames(self, comp_imgs, accumulate_r=None, n_streams=None, fuse_local_min=False, flows=None):
         """process_frame() over a list of frames.  Frames are independent until the merge, so they are
@@ -387,9 +364,11 @@ class BurstPipeline:
             n = len(comp_imgs)
             comp_imgs = self.prefetch(comp_imgs)
             chunks = self._chunks(n, n_streams)
+            if flows is None:
+                flows = self._inject_flows
 
             def work(ci, wait):
-                fronts = self._front_chunk([comp_imgs[i] for i in chunks[ci]], wait, chunks[ci], flows)
+                fronts = self._grouped(comp_imgs, wait, chunks[ci], flows)
                 if wait is not None:  # the robustness needs the second half of the reference precompute
                     torch.cuda.current_stream(self.device).wait_event(wait)
                 return self._robustness(fronts, accumulate_r if wait is None else None, fuse_local_min)

@@ -107,41 +107,40 @@ def grey_radix_schedule(n, seqs=1, threads=512):
     return list(rec[1:1 + rec[0]])
 
 
+def plan_batch(n):
+    """Spectra held by the plan that a launch of n frames uses.  A plan that serves more than one frame per launch always
+    holds MAX_BATCH spectra — 24 MB each at 12 MP: the callers' chunk sizes vary, e.g. graph.host_chunks, and a plan cannot
+    be replaced while its stream is captured; single frames (the reference frame, per-frame launches) need one."""
+    return _lib.MAX_BATCH if n > 1 else 1
+
+
 def compute_grey_images_batch(imgs, method="FFT"):
-    """compute_grey_images() of several frames of one shape: ONE launch per transform phase for up to
+    """compute_grey_images() of a list of frames of one shape.  "FFT": ONE launch per transform phase for up to
     _lib.MAX_BATCH frames (hhsr_grey_lowpass_batch) instead of three per frame — the per-frame launches are
     latency-bound (row / column transforms that sit at barriers half of the time), a chunk of frames keeps one
     resident round of workgroups busy across the frames' row blocks.  Per frame bit-identical.  Returns a list of
     [H, W] views of one [n, H, W] tensor."""
     imgs = [_lib.f32c(i) for i in imgs]
-    if method != "FFT" or len(imgs) < 2:
+    if method != "FFT":
         return [compute_grey_images(i, method) for i in imgs]
     H, W = imgs[0].shape
     dev = imgs[0].device
-    out = torch.empty((len(imgs), H, W), dtype=torch.float32, device=dev)
-    outs = list(out.unbind(0))
-    # (a plan that serves more than one frame per launch always holds MAX_BATCH spectra — 24 MB each at 12 MP: the
-    # callers' chunk sizes vary, e.g. graph.host_chunks, and a plan cannot be replaced while its stream is captured)
-    plan = _grey_plan(H, W, dev, _lib.MAX_BATCH)
-    _lib.call("hhsr_grey_lowpass_batch", plan.handle, _lib.ptr_array(imgs), _lib.ptr_array(outs), len(imgs),
-              _lib.stream(dev))
+    outs = list(torch.empty((len(imgs), H, W), dtype=torch.float32, device=dev).unbind(0))
+    _lib.call("hhsr_grey_lowpass_batch", _grey_plan(H, W, dev, plan_batch(len(imgs))).handle, _lib.ptr_array(imgs),
+              _lib.ptr_array(outs), len(imgs), _lib.stream(dev))
     return outs
 
 
 def compute_grey_images(img, method):
     """raw -> grey.  "FFT": ideal half-band low-pass (utils_image.py:82-100).  The reference runs a full
     complex FFT, zeroes the outer quarter bands of the shifted spectrum and keeps the real part; here the
-    spectrum is the half spectrum of rocFFT's real transform and the zeroing is the equivalent Hermitian
-    mask applied in place by a HIP kernel (no fftshift copies), so irfft2 returns the same real image.
+    transforms are in-LDS HIP kernels (or rocFFT's real transform) inside libhhsr_hip.so and the zeroing is the
+    equivalent Hermitian mask of the half spectrum (no fftshift copies), so the inverse returns the same real image.
     "decimating": 2x2 mean (utils_image.py:101-112) — only used inside the fused covariance kernel."""
+    if method == "FFT":
+        return compute_grey_images_batch([img])[0]
     img = _lib.f32c(img)
     H, W = img.shape
-    if method == "FFT":
-        # planned rocFFT round trip inside libhhsr_hip.so: r2c -> Hermitian mask (+ normalisation) -> c2r
-        out = torch.empty_like(img)
-        _lib.call("hhsr_grey_lowpass", _grey_plan(H, W, img.device).handle, _lib.ptr(img), _lib.ptr(out),
-                  _lib.stream(img.device))
-        return out
     if method == "FFT_torch":  # same maths through torch.fft (rocFFT behind torch), kept for cross-checking
         spec = torch.fft.rfft2(img)
         _lib.call("hhsr_lowpass_mask_r2c", _lib.ptr(spec), H, W, spec.stride(0), spec.stride(1), _lib.stream())
@@ -186,21 +185,12 @@ def cuda_downsample(th_img, kernel="gaussian", factor=2):
         return th_img
     if kernel != "gaussian":
         raise ValueError("please use gaussian kernel")
-    lead = th_img.shape[:-2]
-    img = _lib.f32c(th_img.reshape(th_img.shape[-2:]))
-    H, W = img.shape
-    taps, ntaps = _taps_for_launch(factor)
-    r = (ntaps - 1) // 2
-    h2, w2 = (H - 2 * r) // factor, (W - 2 * r) // factor
-    if h2 < 1 or w2 < 1:
-        raise ValueError(f"image of shape {(H, W)} is too small to be downsampled by {factor}")
-    out = torch.empty((h2, w2), dtype=torch.float32, device=img.device)
-    _lib.call("hhsr_gauss_decimate", _lib.ptr(img), H, W, W, _lib.ptr(out), w2, factor, taps, ntaps, _lib.stream())
-    return out.reshape(*lead, h2, w2)
+    out = cuda_downsample_batch([th_img.reshape(th_img.shape[-2:])], factor)[0]
+    return out.reshape(*th_img.shape[:-2], *out.shape)
 
 
 def cuda_downsample_batch(imgs, factor=2):
-    """cuda_downsample() of several [H, W] levels of one shape in one launch (hhsr_gauss_decimate_batch); per frame
+    """cuda_downsample() of a list of [H, W] levels of one shape in one launch (hhsr_gauss_decimate_batch); per frame
     bit-identical.  Returns a list of views of one [n, h2, w2] tensor."""
     if factor == 1:
         return list(imgs)
@@ -211,8 +201,7 @@ def cuda_downsample_batch(imgs, factor=2):
     h2, w2 = (H - 2 * r) // factor, (W - 2 * r) // factor
     if h2 < 1 or w2 < 1:
         raise ValueError(f"image of shape {(H, W)} is too small to be downsampled by {factor}")
-    out = torch.empty((len(imgs), h2, w2), dtype=torch.float32, device=imgs[0].device)
-    outs = list(out.unbind(0))
+    outs = list(torch.empty((len(imgs), h2, w2), dtype=torch.float32, device=imgs[0].device).unbind(0))
     _lib.call("hhsr_gauss_decimate_batch", _lib.ptr_array(imgs), len(imgs), H, W, W, _lib.ptr_array(outs), w2, factor,
               taps, ntaps, _lib.stream())
     return outs

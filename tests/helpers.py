@@ -1,4 +1,6 @@
 """Shared test helpers (config construction mirrors tools/refsim/make_goldens.py)."""
+import contextlib
+import ctypes
 import os
 
 import numpy as np
@@ -26,6 +28,35 @@ def base_config(ts=16, scale=2, snr=30.0, metrics=("L2", "L2", "L2", "L2"), **kw
     for k, v in kw.items():
         cfg[k] = v
     return cfg
+
+
+# n_frames argument (position behind the name) of the batch entry points; their single forms carry one frame
+FRAMES_ARG = {"hhsr_grey_lowpass_batch": 3, "hhsr_gauss_decimate_batch": 1, "hhsr_align_level_batch": 6,
+              "hhsr_frame_stats_batch": 1}
+
+
+@contextlib.contextmanager
+def recorded_calls():
+    """Records the library calls that enqueue work while they are made (tests/test_front_end_calls.py): yields the list
+    that receives one [entry, frames, stream] per call — the entry point without a trailing `_batch`, the frames of the
+    launch (only for the entry points of FRAMES_ARG and their single forms), the ordinal of the stream handle in order of
+    first appearance.  Calls without a stream (plan creation and queries: they depend on what ran before) are left out."""
+    from handheld_super_resolution import _lib
+
+    real, records, streams = _lib.call, [], {}
+
+    def call(name, *args):
+        if args and isinstance(args[-1], ctypes.c_void_p):
+            entry = name[:-len("_batch")] if name.endswith("_batch") else name
+            frames = [int(args[FRAMES_ARG[name]])] if name in FRAMES_ARG else [1] if entry + "_batch" in FRAMES_ARG else []
+            records.append([entry, *frames, streams.setdefault(args[-1].value, len(streams))])
+        return real(name, *args)
+
+    _lib.call = call
+    try:
+        yield records
+    finally:
+        _lib.call = real
 
 
 # the bursts of tests/golden/e2e_scales.npz (tools/refsim/make_goldens.py, stage e2e_scales: the reference's own main())

@@ -449,3 +449,48 @@ def test_merge_fusion_decisions(case):
     rank = merge_fusions(cfg, shape, n_comp, accumulate_r, denoiser_on)
     assert all(type(v) is bool for v in rank)
     assert "".join("FT"[v] for v in rank) == want_rank
+
+
+def test_front_groups():
+    """super_resolution.front_groups: a chunk of k frames is ONE launch group when k >= 2, the batched front end is on and
+    either every flow is given on the Bayer robustness path or none is and the alignment takes lists of frames; in every
+    other case (one frame, config.hip.batch: false / timers / a grey method without a list form, some flows given, given
+    flows on the mono or robustness-off paths, an alignment that cannot be batched) it is k groups of one frame."""
+    import itertools
+
+    from handheld_super_resolution.super_resolution import front_groups
+
+    assert front_groups(4, True, 0, True, False, True) == [4]      # the default configuration
+    assert front_groups(4, True, 4, True, False, False) == [4]     # a row slab with the gathered flows: one raw pass
+    assert front_groups(4, True, 4, False, False, True) == [1, 1, 1, 1]
+    assert front_groups(4, True, 4, True, True, True) == [1, 1, 1, 1]
+    assert front_groups(4, True, 2, True, False, True) == [1, 1, 1, 1]
+    assert front_groups(4, True, 0, True, False, False) == [1, 1, 1, 1]
+    assert front_groups(4, False, 0, True, False, True) == [1, 1, 1, 1]
+    assert front_groups(1, True, 0, True, False, True) == [1]
+    assert front_groups(0, True, 0, True, False, True) == []
+    seen = 0
+    for k, batch, flows, rob, mono, batchable in itertools.product((1, 2, 4), (True, False), ("none", "all", "some"),
+                                                                   (True, False), (False, True), (True, False)):
+        if flows == "some" and k == 1:
+            continue  # (one frame has its flow or has none)
+        given = {"none": 0, "all": k, "some": k - 1}[flows]
+        if k < 2 or not batch or flows == "some":
+            want = [1] * k
+        elif flows == "all":
+            want = [k] if (rob and not mono) else [1] * k
+        else:
+            want = [k] if batchable else [1] * k
+        assert front_groups(k, batch, given, rob, mono, batchable) == want, (k, batch, flows, rob, mono, batchable)
+        seen += 1
+    assert seen == 3 * 2 * 3 * 2 * 2 * 2 - 2 * 2 * 2 * 2
+
+
+def test_fft_plan_batch():
+    """A launch of one frame uses a plan of one spectrum, a launch of several frames one of MAX_BATCH (chunk sizes vary and a
+    plan cannot be replaced while its stream is captured)."""
+    from handheld_super_resolution import _lib
+
+    assert utils_image.plan_batch(1) == 1
+    assert utils_image.plan_batch(2) == _lib.MAX_BATCH
+    assert utils_image.plan_batch(_lib.MAX_BATCH) == _lib.MAX_BATCH
