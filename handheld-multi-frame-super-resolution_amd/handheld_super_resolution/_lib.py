@@ -71,6 +71,7 @@ _SIGS = {
     "hhsr_post_expose": [P, P, I, I, FP, I, D, P, I, I, DP, I, P, P],
     "hhsr_mertens": [P, I, I, I, P, SZ, P, P, I, P],
     "hhsr_merge_burst": [PP, PP, PP, PP, I, I, I, I, I, I, I, P, P, U8P, D, I, I, P, P, P, I, I, I, I, I, P],
+    "hhsr_merge_plan_query": [I, I, I, I, U8P, D, I, I, I, I, I, I, I, I, I32P, I],
     "hhsr_clock_probe": [P, L, P],
     "hhsr_merge_burst_chain": [PP, PP, PP, PP, I, I, I, I, I, I, I, P, P, U8P, D, I, I, P, P, P, I, I, P, I, P],
 }
@@ -81,6 +82,9 @@ MAX_FRAMES = 64
 MAX_BATCH = 8  # HHSR_MAX_BATCH: frames per launch of the batched front-end entry points
 MAX_EXPOSURES = 4  # HHSR_MAX_EXPOSURES: exposures per hhsr_post_expose / hhsr_mertens call
 GREY_INFO_LEN = 48  # HHSR_GREY_INFO_LEN: values of the record of hhsr_grey_plan_query / hhsr_grey_plan_info
+MERGE_PLAN_LEN = 8  # HHSR_MERGE_PLAN_LEN: values of the record of hhsr_merge_plan_query
+MERGE_FAMILIES = ("generic", "tile", "x2_v1", "x2_mono", "x2", "x3")  # HHSR_MERGE_FAMILY_*: the record's [0]
+MERGE_GEOM_P2 = 1  # HHSR_MERGE_GEOM_P2: the record's [1]
 
 _lib = None
 

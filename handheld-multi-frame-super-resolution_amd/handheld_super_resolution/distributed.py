@@ -55,7 +55,7 @@ import torch
 import torch.distributed as dist
 
 from .config import hip_opt
-from .merge import merge, merge_burst, merge_fusions, merge_ref, scale_is_pow2
+from .merge import merge, merge_burst, merge_fusions, merge_plan, merge_ref
 
 SLAB_ALIGN = 96  # slabs start on the workgroup grids of all merge kernels: 32 output rows (x2), 48 (x3), 16 (tile kernel)
 HALO = 12        # rows of context beyond slab + |flow|.  r[y] = min of R over y +- 2 (robustness.py:641-686); R[y'] reads
@@ -401,7 +401,7 @@ class HipEngine:
         def fn(acc, ref, covs, *rob):
             if self.denoiser_on:
                 scale, ts = cfg.scale, self.tile_size()
-                S0, S1, row0 = sub_image_rows(r0, r1, scale, H, ts, 0.0, from_top=not scale_is_pow2(scale))
+                S0, S1, row0 = sub_image_rows(r0, r1, scale, H, ts, 0.0, from_top=not merge_plan(cfg, (H, W)).exact_positions)
                 q = 1 if self.pipe.mono else 2  # covariances: one per Bayer quad (monochrome: per pixel)
                 num = torch.zeros((int(round(scale * (S1 - S0))), acc.shape[2], 3), dtype=torch.float32, device=acc.device)
                 den = torch.zeros_like(num)
@@ -446,7 +446,7 @@ class SlabWork:
         sW = round(scale * W)
         # (the per-frame operator path of the denoiser has no row offset: for scales whose positions idx / scale are
         # not exact in float32 its sub-image starts at the top of the frame, where sub-image = full-frame coordinates)
-        S0, S1, row0 = sub_image_rows(r0, r1, scale, H, ts, max_flow_y, from_top=eng.denoiser_on and not scale_is_pow2(scale))
+        S0, S1, row0 = sub_image_rows(r0, r1, scale, H, ts, max_flow_y, from_top=eng.denoiser_on and not merge_plan(cfg, (H, W)).exact_positions)
         self.S0, self.S1, self.row0, self.nrows = S0, S1, row0, r1 - r0
         Hs = S1 - S0
         self.sHs = int(round(scale * Hs))
@@ -471,8 +471,7 @@ class SlabWork:
             self.num = torch.zeros((self.sHs, sW, 3), dtype=torch.float32, device=dev)
             self.den = torch.zeros_like(self.num)
         # (frames arrive in front(): the rule is asked for "some"; finish() copes with a slab that got none)
-        self.fuse_acc, fuse_min = merge_fusions(cfg, (Hs, W), 1, eng.accumulate_r, eng.denoiser_on)
-        self.fuse_min = fuse_min and row0 % slab_align(scale) == 0
+        self.fuse_acc, self.fuse_min = merge_fusions(cfg, (Hs, W), 1, eng.accumulate_r, eng.denoiser_on, rows=(row0, self.nrows))
 
     def front(self, imgs, flows):
         """`imgs`: full frames (their rows [S0, S1) are used); `flows`: their FULL flow fields [ny, nx, 2] (views welcome)."""

@@ -1,5 +1,8 @@
 """Alg. 4 / Alg. 11 accumulation (reference merge.py) plus the fused burst merge."""
 
+import ctypes
+from collections import namedtuple
+
 import torch
 
 from . import _lib
@@ -10,6 +13,7 @@ from .config import hip_opt
 KERNEL_ISO, WEIGHT_F64, FORCE_GENERIC, FORCE_TILE, FORCE_X2V1, SENSOR_MONO = 1, 2, 4, 8, 16, 32
 REF_DIVIDE, REF_FAST = 64, 128  # hhsr_accumulate_ref only (include/hhsr.h HHSR_REF_DIVIDE, HHSR_REF_FAST)
 _FORCE = {"auto": 0, "generic": FORCE_GENERIC, "tile": FORCE_TILE, "x2_v1": FORCE_X2V1}
+MergePlan = namedtuple("MergePlan", "family exact_positions local_min chain row_align")  # merge_plan()
 
 
 def _common(config):
@@ -66,30 +70,44 @@ def can_fuse_acc_r(config):
     return float(config.scale).is_integer()
 
 
-def can_fuse_local_min(config, shape):
-    """merge_burst can take the thresholded maps R and apply the 5x5 local minimum itself (the wave-per-parity-class
-    kernels: scale 2, or scale 3 with W % 4 == 0; tile size a multiple of 16; float32 weights) — mirrors the test in
-    hhsr_merge_burst."""
+def merge_plan(config, shape, n_frames=1, rows=None, flags=0):
+    """What hhsr_merge_burst does with `n_frames` comp frames of `shape`, asked of the library (hhsr_merge_plan_query: host
+    only, the rule the launch runs): the kernel family (_lib.MERGE_FAMILIES), whether positions idx / scale are exact in
+    float32, whether the launch can take the 5x5 local minimum itself / be a link of merge_burst_chain, the row granularity
+    of the family's grid.  `rows`: as in merge_burst.  Outputs are taken to be 16-byte aligned (torch allocations)."""
     scale, kflags = _common(config)
-    H, W = shape
-    ok = not (kflags & (WEIGHT_F64 | FORCE_GENERIC | FORCE_TILE)) and int(config.block_matching.tuning.tile_size) % 16 == 0
-    if kflags & SENSOR_MONO:  # monochrome: the x2 tile kernel only
-        return ok and scale == 2.0 and not (kflags & FORCE_X2V1)
-    return ok and ((scale == 2.0 and H % 2 == 0 and W % 2 == 0) or (scale == 3.0 and W % 4 == 0 and _is_bayer(config)))
+    H, W, mono = int(shape[0]), int(shape[1]), bool(kflags & SENSOR_MONO)
+    sH, sW = round(scale * H), round(scale * W)
+    row0, nrows = (0, sH) if rows is None else rows
+    rec = (ctypes.c_int32 * _lib.MERGE_PLAN_LEN)()
+    _lib.call("hhsr_merge_plan_query", int(n_frames), H, W, int(config.block_matching.tuning.tile_size),
+              None if mono else _lib.cfa_bytes(config.exif.cfa_pattern), scale, kflags, int(flags), sH, sW, int(row0),
+              int(nrows), 16, 16, rec, _lib.MERGE_PLAN_LEN)
+    # Two launches the library accepts and this package has never made (tests/golden/merge_decisions.json pins its
+    # answers): the first-generation x2 kernel on a monochrome sensor, and x2 of Bayer frames with an odd height or width.
+    unused = bool(mono and kflags & FORCE_X2V1) or (not mono and scale == 2.0 and (H % 2 != 0 or W % 2 != 0))
+    return MergePlan(_lib.MERGE_FAMILIES[rec[0]], rec[1] == _lib.MERGE_GEOM_P2, *(bool(v) and not unused for v in rec[2:4]), rec[4])
 
 
-def merge_fusions(config, shape, n_comp, accumulate_r, denoiser_on):
+def can_fuse_local_min(config, shape):
+    """merge_burst can take the thresholded maps R and apply the 5x5 local minimum itself (merge_plan)."""
+    return merge_plan(config, shape).local_min
+
+
+def can_chain(config, shape):
+    """merge_burst_chain applies (merge_plan)."""
+    return merge_plan(config, shape).chain
+
+
+def merge_fusions(config, shape, n_comp, accumulate_r, denoiser_on, rows=None):
     """(fuse_acc, fuse_min): the fused merge of `n_comp` frames of `shape` also sums the robustness maps / takes their 5x5
     local minimum itself — the ONE rule of main(), the host-resident runner and both multi-GPU strategies.  The denoiser
-    decides on a float64 sum, not the merge's float32 one; a map accumulated apart from the merge needs the filtered maps."""
+    decides on a float64 sum, not the merge's float32 one; a map accumulated apart from the merge needs the filtered maps.
+    `rows = (row0, nrows)`: the launch covers this slab of output rows (merge_burst)."""
     fuse_acc = bool(accumulate_r and not denoiser_on and n_comp > 0 and can_fuse_acc_r(config))
-    fuse_min = bool(config.robustness.enabled and can_fuse_local_min(config, shape) and (fuse_acc or not accumulate_r))
+    fuse_min = bool(config.robustness.enabled and merge_plan(config, shape, rows=rows).local_min and
+                    (fuse_acc or not accumulate_r))
     return fuse_acc, fuse_min
-
-
-def scale_is_pow2(scale):
-    """1, 2, 4, 8: (h + 0.5) / scale is exact in float32 — mirrors scale_is_pow2() of hhsr_merge.hip."""
-    return float(scale) in (1.0, 2.0, 4.0, 8.0)
 
 
 def merge_burst(frames, ref_img, ref_kernels, num, den, cfa_pattern, config, load_acc=False, do_ref=True,
@@ -139,25 +157,6 @@ def merge_burst(frames, ref_img, ref_kernels, num, den, cfa_pattern, config, loa
                   H, W, W, ny, nx, int(ts), _lib.ptr(ref_img if (f & 2) else None),
                   _lib.ptr(ref_kernels if (f & 2) else None), cfa, scale, kflags, f, _lib.ptr(num), _lib.ptr(den),
                   _lib.ptr(acc_r if chunk else None), sH, sW, int(row0), int(nrows), int(lr_row_offset), _lib.stream())
-
-
-def _is_bayer(config):
-    """2 x 2 colour layout with red and blue on one diagonal and green on the other (what the wave-per-class kernels
-    fold their parity classes into; other layouts take the first-generation tile kernels) — mirrors cfa_is_bayer()."""
-    try:
-        c = [int(v) for row in config.exif.cfa_pattern for v in row]
-    except Exception:
-        return False
-    for k in range(4):
-        if c[k] == 0:
-            return c[3 - k] == 2 and c[k ^ 1] == 1 and c[k ^ 2] == 1
-    return False
-
-
-def can_chain(config, shape):
-    """merge_burst_chain applies: the wave-per-class x2 kernel (same conditions as can_fuse_local_min at scale 2, Bayer)."""
-    scale, kflags = _common(config)
-    return scale == 2.0 and not (kflags & SENSOR_MONO) and can_fuse_local_min(config, shape) and _is_bayer(config)
 
 
 def chain_buffer(shape, device):

@@ -335,10 +335,7 @@ int hhsr_add(float* A, const float* B, int64_t n, void* stream);          /* A +
  * ONE `pitch` (>= W, odd allowed, 4-byte aligned bases) for all comp frames raws[] AND ref_raw; flows, covs, rs, ref_covs,
  * acc_r, num and den are compact.  For a sub-image, raws[n] / ref_raw point at the sub-image's first row inside the
  * full frame (pitch unchanged) and the other arrays at their matching rows.
- * Kernel choice (float32 weights): scale 2 and scale 3 with a BAYER cfa (red and blue on one diagonal, green on the other),
- * ts % 16 == 0 and even / exact output sizes run the wave-per-parity-class kernels (three channel accumulators per
- * sub-pixel; scale 3: frames whose window leaves the image are evaluated by the same code with border masks); other
- * 2 x 2 colour layouts and other integer scales the 16 x 16 tile kernels; non-integer scales the per-pixel kernel.
+ * Which kernel runs: hhsr_merge_plan_query below.
  * flags: */
 #define HHSR_MERGE_LOAD_ACC 1   /* start from the existing num/den instead of zero          */
 #define HHSR_MERGE_DO_REF 2     /* add the reference frame (ref_raw/ref_covs) after the comps */
@@ -355,6 +352,36 @@ int hhsr_merge_burst(const float* const* raws, const float* const* flows, const 
                      const uint8_t cfa[4], double scale, int kflags, int flags,
                      float* num, float* den, float* acc_r, int sH, int sW, int row0, int nrows,
                      int lr_row_offset, void* stream);
+
+/* Kernel choice of hhsr_merge_burst: what a launch with the same n_frames, H, W, ts, cfa (HOST), scale, kflags, flags, sH, sW,
+ * row0 and nrows does, decided by the code the launch itself runs.  num_align / den_align: byte alignment of the launch's
+ * num / den (16 or a multiple: 16-byte aligned; den_align counts only with HHSR_MERGE_STORE_DEN).  Host only: no HIP call,
+ * usable without a device.  Invalid arguments return -1 as in the launch.  out (HOST, n >= HHSR_MERGE_PLAN_LEN values):
+ *   [0] the kernel family.  With float32 weights, scale 2 and scale 3 with a BAYER cfa (red and blue on one diagonal, green on
+ *       the other), ts % 16 == 0 and even / exact output sizes run the wave-per-parity-class kernels (three channel
+ *       accumulators per sub-pixel; scale 3, which also needs W % 4 == 0 and 16-byte aligned outputs: frames whose window
+ *       leaves the image are evaluated by the same code with border masks); other 2 x 2 colour layouts, unaligned outputs and
+ *       monochrome sensors at scale 2 the first-generation x2 kernels; other integer scales with (ts scale) % 16 == 0 the
+ *       16 x 16 tile kernel; everything else (non-integer scales, HHSR_WEIGHT_F64, no comp frame, a row0 off the
+ *       family's grid, monochrome at other scales) the per-pixel kernel
+ *   [1] position arithmetic of the float32 kernels at this scale: HHSR_MERGE_GEOM_P2 = idx / scale is exact in float32
+ *       (scales 1, 2, 4, 8), HHSR_MERGE_GEOM_F64 = evaluated in float64 (with HHSR_WEIGHT_F64 always in float64)
+ *   [2] 1 = these arguments admit HHSR_MERGE_LOCAL_MIN, [3] 1 = they admit a link of hhsr_merge_burst_chain
+ *   [4] output rows per workgroup row of the family's grid (1, 16, 32 or 48): row0 has to be a multiple for the family to run
+ *   [5] / [6] the grid's x / y size
+ *   [7] what the launch returns for `flags` before it enqueues anything: 0, or -3 (HHSR_MERGE_LOCAL_MIN or a chain link asked
+ *       for and not admitted; hhsr_last_error() then holds the launch's message). */
+#define HHSR_MERGE_FAMILY_GENERIC 0  /* k_merge_burst: one thread per HR pixel                                 */
+#define HHSR_MERGE_FAMILY_TILE 1     /* k_merge_burst_tile: 16 x 16 HR pixels through LDS                      */
+#define HHSR_MERGE_FAMILY_X2V1 2     /* k_merge_burst_quad: first-generation x2                                */
+#define HHSR_MERGE_FAMILY_X2_MONO 3  /* its monochrome form                                                    */
+#define HHSR_MERGE_FAMILY_X2 4       /* k_merge_x2                                                             */
+#define HHSR_MERGE_FAMILY_X3 5       /* k_merge_xs<3>                                                          */
+#define HHSR_MERGE_GEOM_F64 0
+#define HHSR_MERGE_GEOM_P2 1
+#define HHSR_MERGE_PLAN_LEN 8
+int hhsr_merge_plan_query(int n_frames, int H, int W, int ts, const uint8_t cfa[4], double scale, int kflags, int flags,
+                          int sH, int sW, int row0, int nrows, int num_align, int den_align, int32_t* out, int n);
 
 /* The fused x2 merge as a CHAIN of launches for bursts whose last frames arrive late (frames crossing PCIe: the early links
  * run while the late frames upload), bit-identical to ONE hhsr_merge_burst over all frames.  Every link gets the frames

@@ -1,4 +1,7 @@
 """Host-side logic (config shim, parameter derivation, level shapes, filter taps) — CPU only."""
+import json
+import os
+
 import numpy as np
 import pytest
 
@@ -449,6 +452,149 @@ def test_merge_fusion_decisions(case):
     rank = merge_fusions(cfg, shape, n_comp, accumulate_r, denoiser_on)
     assert all(type(v) is bool for v in rank)
     assert "".join("FT"[v] for v in rank) == want_rank
+
+
+DECISIONS_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "merge_decisions.json")
+DECISION_AXES = [  # iteration order of the fixture: itertools.product of these, the last axis fastest
+    ("scale", [1, 1.5, 2, 3, 4, 5]),
+    ("tile_size", [8, 16, 32]),
+    ("mode", ["bayer", "grey"]),
+    ("cfa", [[[0, 1], [1, 2]], [[2, 1], [1, 0]], [[1, 0], [2, 1]], [[0, 2], [1, 1]]]),
+    ("merge_kernel", ["auto", "generic", "tile", "x2_v1"]),
+    ("weight_fp64", [False, True]),
+    ("shape", [[64, 64], [64, 66], [63, 64]]),
+]
+# per row of the product: one letter for can_fuse_local_min, one for can_chain, two (fuse_acc, fuse_min) for each
+# merge_fusions(config, shape, 3, accumulate_r, denoiser_on)
+DECISION_ANSWERS = ["can_fuse_local_min", "can_chain", "merge_fusions_FF", "merge_fusions_TF", "merge_fusions_TT"]
+
+
+def _merge_decisions():
+    import itertools
+
+    from handheld_super_resolution import merge
+
+    out = {name: [] for name in DECISION_ANSWERS}
+    for scale, ts, mode, cfa, kernel, f64, shape in itertools.product(*(values for _, values in DECISION_AXES)):
+        cfg = base_config(ts=ts, scale=scale, mode=mode, hip={"merge_kernel": kernel, "weight_fp64": f64})
+        cfg.exif.cfa_pattern = cfa
+        shape = tuple(shape)
+        out["can_fuse_local_min"].append("FT"[bool(merge.can_fuse_local_min(cfg, shape))])
+        out["can_chain"].append("FT"[bool(merge.can_chain(cfg, shape))])
+        for name, (acc, den) in zip(DECISION_ANSWERS[2:], ((False, False), (True, False), (True, True))):
+            out[name].append("".join("FT"[bool(v)] for v in merge.merge_fusions(cfg, shape, 3, acc, den)))
+    return {name: "".join(letters) for name, letters in out.items()}
+
+
+def test_merge_decisions_are_the_recorded_ones():
+    """can_fuse_local_min, can_chain and merge_fusions over 3456 configurations against tests/golden/merge_decisions.json:
+    the answers of the commit BEFORE merge.py asked the library (hhsr_merge_plan_query) instead of restating its rule.
+    The fixture was written at that commit, with tests/ and the package folder on PYTHONPATH, by
+
+        import json, test_host_logic as t
+        json.dump({"axes": t.DECISION_AXES, "answers": t._merge_decisions()}, open(t.DECISIONS_GOLDEN, "w"), indent=0)
+
+    and only a change that means to alter what a burst's merge fuses regenerates it.
+
+    One answer is NOT kept, because it promised a launch the library refuses: that commit said can_chain with
+    merge_kernel: x2_v1 (12 rows), and hhsr_merge_burst_chain returns -1 for HHSR_MERGE_FORCE_X2V1 — the first-generation
+    kernel has no parity-class accumulators to park.  Those rows follow the library: F."""
+    import itertools
+
+    with open(DECISIONS_GOLDEN) as f:
+        golden = json.load(f)
+    assert golden["axes"] == [list(axis) for axis in DECISION_AXES]
+    got = _merge_decisions()
+    kernels = [row[4] for row in itertools.product(*(values for _, values in DECISION_AXES))]
+    for name in DECISION_ANSWERS:
+        want = golden["answers"][name]
+        if name == "can_chain":
+            refused = [i for i, k in enumerate(kernels) if k == "x2_v1" and want[i] == "T"]
+            assert len(refused) == 12
+            want = "".join("F" if k == "x2_v1" else w for w, k in zip(want, kernels))
+        assert len(want) == len(got[name]) == len(kernels) * (1 if name.startswith("can_") else 2)
+        wrong = [i for i, (a, b) in enumerate(zip(want, got[name])) if a != b]
+        assert not wrong, (name, len(wrong), wrong[:8])
+    assert set(golden["answers"]["can_chain"]) == {"F", "T"}  # (both answers occur: the product reaches the rule)
+
+
+def test_merge_plan_query_follows_the_launch_rule():
+    """hhsr_merge_plan_query (host only, the rule hhsr_merge_burst launches by): the family per case, the row granularity
+    and grid that go with it, what HHSR_MERGE_LOCAL_MIN and a chain link get, and the argument errors."""
+    import ctypes
+
+    from handheld_super_resolution import _lib
+    from handheld_super_resolution.merge import FORCE_GENERIC, FORCE_TILE, FORCE_X2V1, SENSOR_MONO, WEIGHT_F64
+
+    lib = _lib.load()
+    bayer, other = [[2, 1], [1, 0]], [[0, 2], [1, 1]]
+
+    def query(scale, W=64, cfa=bayer, kflags=0, flags=0, row0=0, nrows=None, align=16, n=_lib.MERGE_PLAN_LEN, out=True,
+              n_frames=2, ts=16):
+        H = 64
+        sH, sW = round(scale * H), round(scale * W)
+        rec = (ctypes.c_int32 * _lib.MERGE_PLAN_LEN)(*([-9] * _lib.MERGE_PLAN_LEN))
+        rc = lib.hhsr_merge_plan_query(n_frames, H, W, ts, _lib.cfa_bytes(cfa), float(scale), kflags, flags, sH, sW, row0,
+                                       sH - row0 if nrows is None else nrows, align, align, rec if out else None, n)
+        return rc, dict(family=_lib.MERGE_FAMILIES[rec[0]] if rc == 0 else None, p2=rec[1] == _lib.MERGE_GEOM_P2,
+                        local_min=rec[2], chain=rec[3], row_align=rec[4], grid=(rec[5], rec[6]), code=rec[7])
+
+    # (arguments, family, local_min, chain, rows per workgroup row, grid)
+    table = [
+        (dict(scale=2), "x2", 1, 1, 32, (4, 4)),
+        (dict(scale=2, cfa=other), "x2_v1", 1, 0, 32, (4, 4)),
+        (dict(scale=2, kflags=SENSOR_MONO), "x2_mono", 1, 0, 32, (4, 4)),
+        (dict(scale=3), "x3", 1, 0, 48, (4, 4)),
+        (dict(scale=3, W=66), "tile", 0, 0, 16, (13, 12)),       # W % 4 == 2
+        (dict(scale=3, cfa=other), "tile", 0, 0, 16, (12, 12)),
+        (dict(scale=4), "tile", 0, 0, 16, (16, 16)),
+        (dict(scale=1.5), "generic", 0, 0, 1, (2, 24)),
+        (dict(scale=2, kflags=FORCE_GENERIC), "generic", 0, 0, 1, (2, 32)),
+        (dict(scale=2, kflags=FORCE_TILE), "tile", 0, 0, 16, (8, 8)),
+        (dict(scale=3, kflags=FORCE_TILE), "tile", 0, 0, 16, (12, 12)),
+        (dict(scale=2, kflags=FORCE_X2V1), "x2_v1", 1, 0, 32, (4, 4)),
+        (dict(scale=2, kflags=FORCE_X2V1 | SENSOR_MONO), "x2_mono", 1, 0, 32, (4, 4)),
+        (dict(scale=2, kflags=WEIGHT_F64), "generic", 0, 0, 1, (2, 32)),
+        (dict(scale=2, row0=32), "x2", 1, 0, 32, (4, 3)),       # a slab on the x2 grid: no chain link (whole images only)
+        (dict(scale=2, row0=16), "tile", 0, 0, 16, (8, 7)),
+        (dict(scale=2, row0=8), "generic", 0, 0, 1, (2, 30)),
+        (dict(scale=2, nrows=33), "tile", 0, 0, 16, (8, 3)),    # an odd number of rows
+        (dict(scale=3, row0=48), "x3", 1, 0, 48, (4, 3)),
+        (dict(scale=3, row0=32), "tile", 0, 0, 16, (12, 10)),
+        (dict(scale=2, align=4), "x2_v1", 1, 0, 32, (4, 4)),     # an output that is not 16-byte aligned
+        (dict(scale=3, align=4), "tile", 0, 0, 16, (12, 12)),
+        (dict(scale=2, ts=8), "tile", 0, 0, 16, (8, 8)),
+        (dict(scale=3, ts=8), "generic", 0, 0, 1, (3, 48)),
+        (dict(scale=3, kflags=SENSOR_MONO), "generic", 0, 0, 1, (3, 48)),
+        (dict(scale=2, n_frames=0), "generic", 0, 0, 1, (2, 32)),  # the reference frame alone
+    ]
+    for args, family, local_min, chain, row_align, grid in table:
+        rc, got = query(**args)
+        assert rc == 0, args
+        assert got == dict(family=family, p2=args["scale"] in (1, 2, 4, 8), local_min=local_min, chain=chain,
+                           row_align=row_align, grid=grid, code=0), (args, got)
+        # flags that ask for what the arguments do not admit: the launch's -3 and its message, nothing else changes
+        rc, asked = query(flags=_lib.MERGE_LOCAL_MIN, **args)
+        assert rc == 0 and asked == dict(got, code=0 if local_min else -3), (args, asked)
+        if not local_min:
+            assert b"HHSR_MERGE_LOCAL_MIN needs the x2 or the x3 kernel" in lib.hhsr_last_error()
+        rc, asked = query(flags=_lib.MERGE_STORE_CLASSES, **args)
+        assert rc == 0 and asked == dict(got, code=0 if chain else -3), (args, asked)
+        if not chain:
+            assert b"needs the wave-per-class x2 kernel" in lib.hhsr_last_error()
+    # den counts only when it is stored
+    assert query(2, align=16)[1]["family"] == "x2"
+    rec = (ctypes.c_int32 * _lib.MERGE_PLAN_LEN)()
+    for flags, family in ((0, "x2"), (_lib.MERGE_STORE_DEN, "x2_v1")):
+        assert lib.hhsr_merge_plan_query(2, 64, 64, 16, _lib.cfa_bytes(bayer), 2.0, 0, flags, 128, 128, 0, 128, 16, 4, rec,
+                                         _lib.MERGE_PLAN_LEN) == 0
+        assert _lib.MERGE_FAMILIES[rec[0]] == family
+    # argument errors: host side, -1 like the launch, the record untouched
+    for bad in (dict(n=_lib.MERGE_PLAN_LEN - 1), dict(out=False), dict(scale=0.5), dict(nrows=129), dict(nrows=0), dict(row0=-16),
+                dict(n_frames=_lib.MAX_FRAMES + 1), dict(ts=0), dict(cfa=[[0, 1], [1, 3]])):
+        rc, got = query(**dict(dict(scale=2), **bad))
+        assert rc == -1 and b"invalid argument" in lib.hhsr_last_error(), bad
+        assert got["code"] == -9, bad
 
 
 def test_front_groups():

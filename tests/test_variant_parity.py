@@ -12,6 +12,8 @@ the oracle on identical inputs, on grids that give the XCD-aware workgroup remap
 
 Tolerances are the ones of tests/test_hip_parity.py for the same stages (merge rtol 2e-5 / atol 1e-6, flows 2e-4 px
 with the block-matching near-tie rule, grey 3e-6, robustness 1e-4)."""
+import itertools
+
 import numpy as np
 import pytest
 import torch
@@ -19,7 +21,7 @@ import torch
 import oracle
 from oracle import cfast
 from oracle.parallel import available_cores
-from helpers import assert_close, base_config, bm_inputs, check_bm, smooth
+from helpers import assert_close, base_config, bm_inputs, check_bm, merge_frames, smooth
 
 pytestmark = pytest.mark.gpu
 
@@ -284,6 +286,80 @@ def test_merge_x4_more_frames_than_one_launch_holds():
     with np.errstate(all="ignore"):
         assert_close(N(out), num.astype(np.float64) / den, *TOL, "x4 70-frame burst")
     assert_close(N(acc), _acc_want(frames), 1e-6, 1e-6, "x4 70-frame accumulated robustness")
+
+
+PLAN_CFAS = {"rggb": [[0, 1], [1, 2]], "bggr": [[2, 1], [1, 0]], "grbg": [[1, 0], [2, 1]], "rbgg": [[0, 2], [1, 1]], "grey": None}
+PLAN_SLABS = {1.5: [None], 2: [None, (32, 32), (16, 32)], 3: [None, (48, 48)], 4: [None]}  # of 64 (x2) / 96 (x3) output rows
+
+
+@pytest.mark.parametrize("W,ts", [(32, 16), (34, 16), (32, 8), (34, 8)])
+def test_merge_plan_matches_launch(W, ts):
+    """The record of hhsr_merge_plan_query against what the launch does with the same arguments, on real buffers of
+    the right sizes: 32 x W raw pixels (two flow tiles per axis at ts 16; W = 34: W % 4 == 2 takes x3 off the x3 kernel),
+    2 comp frames, scales 1.5 / 2 / 3 / 4, three Bayer layouts, a non-Bayer one and `mode: grey`, every merge_kernel, the
+    whole image and row slabs on and off the x2 / x3 workgroup grids.  A launch with HHSR_MERGE_LOCAL_MIN returns 0 exactly
+    where the record's local_min field is 1 and -3 exactly where it is 0 (refusals return before any HIP call); where it
+    runs, its image equals robustness.local_min followed by the plain launch, bit for bit.  The first link of
+    hhsr_merge_burst_chain likewise against the chain field — with one difference the entry point's own argument check
+    makes: for a monochrome sensor or a forced kernel it refuses with -1 ("invalid argument") before it reaches the plan."""
+    import ctypes
+
+    H = 32
+    lib = _lib.load()
+    inputs = {}
+    for mode in ("bayer", "grey"):
+        cfg = base_config(ts=ts, scale=2, mode=mode)
+        ref, fr = merge_frames(H, W, 2, ts, 91, cfg)
+        tf = [tuple(T(a) for a in f) for f in fr]
+        inputs[mode] = (T(ref), T(oracle.estimate_kernels(ref, cfg)), tf,
+                        [(f[0], f[1], f[2], robustness.local_min(f[3])) for f in tf])
+    cls = merge.chain_buffer((H, W), torch.device(DEV))
+    seen = {"min": set(), "chain": set()}
+    for scale, (sensor, cfa), kernel in itertools.product(PLAN_SLABS, PLAN_CFAS.items(), ("auto", "generic", "tile", "x2_v1")):
+        mode = "grey" if sensor == "grey" else "bayer"
+        cfg = base_config(ts=ts, scale=scale, mode=mode, hip={"merge_kernel": kernel})
+        cfa = cfa or [[1, 1], [1, 1]]
+        cfg.exif.cfa_pattern = cfa
+        ref, ref_covs, tf, tf_min = inputs[mode]
+        sH, sW = round(scale * H), round(scale * W)
+        fscale, kflags = merge._common(cfg)
+
+        def record(rows, flags):
+            rec = (ctypes.c_int32 * _lib.MERGE_PLAN_LEN)()
+            assert lib.hhsr_merge_plan_query(2, H, W, ts, _lib.cfa_bytes(cfa), fscale, kflags, flags, sH, sW, *rows, 16, 16,
+                                             rec, _lib.MERGE_PLAN_LEN) == 0
+            return list(rec)
+
+        for rows in PLAN_SLABS[scale]:
+            what = (scale, sensor, kernel, rows)
+            row0, nrows = rows or (0, sH)
+            rec = record((row0, nrows), _lib.MERGE_DO_REF | _lib.MERGE_DIVIDE)
+            assert rec[7] == 0 and row0 % rec[4] == 0, (what, rec)
+            assert record((row0, nrows), _lib.MERGE_DO_REF | _lib.MERGE_DIVIDE | _lib.MERGE_LOCAL_MIN)[7] == (0 if rec[2] else -3)
+            kw = dict(rows=rows, out_height=sH) if rows else {}
+            got = torch.full((nrows, sW, 3), -7.0, device=DEV)
+            assert got.data_ptr() % 16 == 0
+            seen["min"].add(rec[2])
+            if rec[2]:
+                merge.merge_burst(tf, ref, ref_covs, got, None, cfa, cfg, local_min=True, **kw)
+                want = torch.full_like(got, -7.0)
+                merge.merge_burst(tf_min, ref, ref_covs, want, None, cfa, cfg, **kw)
+                assert torch.equal(torch.nan_to_num(got, nan=-1.0), torch.nan_to_num(want, nan=-1.0)), what
+                assert not (got == -7.0).any(), what
+            else:
+                with pytest.raises(RuntimeError, match=r"code -3\).*HHSR_MERGE_LOCAL_MIN needs"):
+                    merge.merge_burst(tf, ref, ref_covs, got, None, cfa, cfg, local_min=True, **kw)
+            if rows is None:
+                seen["chain"].add(rec[3])
+                assert record((0, sH), _lib.MERGE_STORE_CLASSES)[7] == (0 if rec[3] else -3)
+                if rec[3]:
+                    merge.merge_burst_chain(tf[:1], 0, None, None, got, cfa, cfg, cls, False)
+                else:
+                    code = -1 if (mode == "grey" or kernel != "auto") else -3
+                    with pytest.raises(RuntimeError, match=rf"code {code}\)"):
+                        merge.merge_burst_chain(tf[:1], 0, None, None, got, cfa, cfg, cls, False)
+    torch.cuda.synchronize()
+    assert seen["min"] == ({0, 1} if ts == 16 else {0}) and seen["chain"] == ({0, 1} if ts == 16 else {0})
 
 
 # ------------------------------------------------------------------------------------------ alignment
