@@ -21,6 +21,7 @@ PP = C.POINTER(C.c_void_p)
 I32P = C.POINTER(C.c_int32)
 SZ = C.c_size_t
 SZP = C.POINTER(C.c_size_t)
+I64P = C.POINTER(C.c_int64)
 
 # name -> argtypes (all return int)
 _SIGS = {
@@ -48,6 +49,8 @@ _SIGS = {
     "hhsr_frame_stats": [P, I, I, I, U8P, DP, P, P, P, D, D, D, D, D, D, D, D, I, P],
     "hhsr_frame_stats_batch": [PP, I, I, I, I, U8P, DP, PP, PP, D, D, D, D, D, D, D, D, I, P],
     "hhsr_normalize_raw_u16": [P, I, I, I, I, U8P, DP, D, DP, P, P],
+    "hhsr_normalize_raw_packed": [P, I, I, I, L, L, I, U8P, DP, D, DP, P, P],
+    "hhsr_packed_row_bytes": [I, I, I64P],
     "hhsr_rob_upscale": [P, I, I, P, I, I, I, P, P],
     "hhsr_rob_s": [P, I, I, D, F, F, P, I, I, P],
     "hhsr_rob_sigma": [P, P, I, I, P, I, P, P, P],

@@ -249,7 +249,8 @@ HIP_KNOBS = {
     "merge_link_after": None,  # ... explicit chunk indices after which a link runs (tuning)
     "host_chunk_sizes": None,  # ... explicit chunk sizes (tuning)
     "inject_flows": None,      # per-frame flow fields that replace the alignment (validation)
-    "raw_norm": None,          # {"black_levels", "white_level"} of frames given as integer sensor counts
+    "raw_norm": None,          # {"black_levels", "white_level"} of frames given as integer sensor counts; + "packing" (a
+    #                            name of utils_dng.PACKINGS) and "width" for uint8 frames of packed 10/12/14-bit rows
     "max_flow": None,          # multi-GPU "rows": bound on |flow_y|; measured when absent
     "align_cost": None,        # multi-GPU "rows": distributed.align_cost(scale)
 }

@@ -153,7 +153,10 @@ class BurstPipeline:
         """One frame -> float32 device tensor, on the current stream.  Float frames are the reference's call signature
         (normalised, white-balanced RAW).  Integer frames are sensor counts as the DNG holds them: they are uploaded as
         they are — half the PCIe bytes of the float32 frame — and normalised on the device with the reference loader's
-        arithmetic (utils_dng.py:149-160, hhsr_normalize_raw_u16) using config.hip.raw_norm and config.exif."""
+        arithmetic (utils_dng.py:149-160, hhsr_normalize_raw_u16) using config.hip.raw_norm and config.exif.  With
+        raw_norm["packing"] (a name of utils_dng.PACKINGS) and raw_norm["width"], uint8 frames [H, row_bytes] are the
+        packed 10/12/14-bit counts themselves — 1.25 to 1.75 bytes per pixel over PCIe — and hhsr_normalize_raw_packed
+        unpacks and normalises them in one pass."""
         staged = isinstance(img, _Staged)
         if staged:  # prefetch(): the copy was queued on the upload stream
             if img.event is not None:  # (None: a static staging buffer of graph.HostBurstRunner, ordered by the runner)
@@ -167,8 +170,12 @@ class BurstPipeline:
         if (t.is_cuda and not staged) or self._raw_norm is None:
             raise ValueError("integer frames are sensor counts: give config.hip.raw_norm = {black_levels, white_level} "
                              "(host arrays), or pass normalised float frames")
-        from .utils_dng import normalize_burst
+        from .utils_dng import normalize_burst, normalize_packed, packed_width
 
+        width = packed_width(self._raw_norm, t)
+        if width is not None:  # raw_norm["packing"]: the 10/12/14-bit bytes as the sensor or the DNG holds them
+            return normalize_packed(t, width, self._raw_norm["packing"], self._raw_norm["black_levels"],
+                                    self._raw_norm["white_level"], self.wb, self.cfa, device=self.device)
         return normalize_burst(t, self._raw_norm["black_levels"], self._raw_norm["white_level"], self.wb, self.cfa,
                                device=self.device)
 
@@ -641,7 +648,9 @@ def process(burst_path, config):
     ``iso``, ``std_curve``, ``diff_curve``, ``orientation`` (EXIF 1..8), ``xyz2cam`` (3x3, DNG ColorMatrix1, for
     ``postprocessing.do_color_correction``) — ``cfa_pattern`` / ``white_balance`` may be left out with ``mode: grey``
     (monochrome sensors: channel 0 of the result is the image, channels 1 and 2 are NaN like the reference's); ref / comp are either normalised white-balanced float RAW or integer
-    sensor counts with ``black_levels`` and ``white_level`` (normalised on the GPU like utils_dng.py:149-160) —
+    sensor counts with ``black_levels`` and ``white_level`` (normalised on the GPU like utils_dng.py:149-160), either
+    uint16 or, with ``packing`` (a name of utils_dng.PACKINGS) and ``width`` (may be left out when the rows hold no
+    padding), the packed 10/12/14-bit rows as uint8 [H, row_bytes] —
     or a folder of .dng files, which needs rawpy + exifread like the reference (absent from this image:
     ImportError).  Noise curves: given in the burst, or ``config.noise_model.estimator``: "monte_carlo" (default — the
     reference's estimator run_fast_MC, super_resolution.py:252, whose curves include the clipping of the noisy samples
@@ -654,7 +663,7 @@ def process(burst_path, config):
     finished image is copied to the host."""
     import os
 
-    from .utils_dng import load_dng_burst, normalize_burst
+    from .utils_dng import infer_width, load_dng_burst, normalize_burst, normalize_packed
 
     if isinstance(burst_path, (str, os.PathLike)) and str(burst_path).endswith(".npz"):
         burst = dict(np.load(burst_path))
@@ -683,10 +692,20 @@ def process(burst_path, config):
         # reference frame now (its brightness picks the SNR-based parameters); the other frames stay integer host arrays
         # and are uploaded as counts — half the bytes of float32 frames — and normalised frame by frame on the pipeline
         # streams (BurstPipeline._ingest), overlapping the other frames' kernels
-        ref_raw = normalize_burst(np.asarray(ref_raw), burst["black_levels"], burst["white_level"],
-                                  burst["white_balance"], burst["cfa_pattern"])
-        raw_comp = [np.asarray(f) for f in raw_comp]
         raw_norm = {"black_levels": [float(v) for v in list(burst["black_levels"])[:3]], "white_level": float(burst["white_level"])}
+        if burst.get("packing", None) is not None:  # ref / comp are uint8 packed rows (utils_dng.PACKINGS) and stay so
+            packing = np.asarray(burst["packing"]).item()
+            width = burst.get("width", None)
+            width = infer_width(np.asarray(ref_raw).shape[-1], packing) if width is None else int(np.asarray(width))
+            if width is None:
+                raise ValueError("packed burst: give 'width' (the rows are longer than their pixels' bytes)")
+            ref_raw = normalize_packed(np.asarray(ref_raw), width, packing, burst["black_levels"], burst["white_level"],
+                                       burst["white_balance"], burst["cfa_pattern"])
+            raw_norm.update(packing=packing, width=width)
+        else:
+            ref_raw = normalize_burst(np.asarray(ref_raw), burst["black_levels"], burst["white_level"],
+                                      burst["white_balance"], burst["cfa_pattern"])
+        raw_comp = [np.asarray(f) for f in raw_comp]
         config.hip = dict(getattr(config, "hip", None) or {}, raw_norm=raw_norm)  # (a fresh mapping: the caller's is not edited)
         brightness_src = ref_raw.mean().item()
     else:

@@ -1,6 +1,9 @@
 """Burst front end (reference utils_dng.py:50-164): sensor counts -> normalised, white-balanced
 float32 RAW on the GPU.  DNG *decoding* needs rawpy + exifread like the reference; bursts that are already in
-memory (or in an .npz file) as integer arrays + metadata take the same normalisation without them."""
+memory (or in an .npz file) as integer arrays + metadata take the same normalisation without them — as uint16 counts, or
+as the 10/12/14-bit packed bytes the sensor interface (MIPI CSI-2) or an uncompressed DNG holds, unpacked on the GPU."""
+import ctypes
+
 import numpy as np
 import torch
 
@@ -35,6 +38,126 @@ def normalize_burst(raw, black_levels, white_level, white_balance, cfa_pattern, 
         raise ValueError("black_levels and white_balance need one entry per colour (R, G, B)")
     _lib.call("hhsr_normalize_raw_u16", _lib.ptr(arr), n, H, W, W, _lib.cfa_bytes(cfa_pattern), _lib.doubles(bl),
               float(white_level), _lib.doubles(wb), _lib.ptr(out), _lib.stream())
+    return out[0] if squeeze else out
+
+
+# Packed layouts of hhsr_normalize_raw_packed (include/hhsr.h states them operation by operation): name -> id
+PACKINGS = {"mipi10": 1, "mipi12": 2, "mipi14": 3, "be10": 4, "be12": 5, "be14": 6}
+
+
+def _packing(packing):
+    """(id, bits, big-endian bit stream?) of a layout given by name or id."""
+    pid = PACKINGS.get(packing) if isinstance(packing, str) else (int(packing) if int(packing) in PACKINGS.values() else None)
+    if pid is None:
+        raise ValueError(f"packing {packing!r}: one of {sorted(PACKINGS)}")
+    return pid, 10 + 2 * ((pid - 1) % 3), pid >= 4
+
+
+def packed_row_bytes(width, packing):
+    """Bytes one packed row of `width` pixels occupies (the library's rule: hhsr_packed_row_bytes, no GPU needed)."""
+    out = ctypes.c_int64()
+    _lib.call("hhsr_packed_row_bytes", int(width), _packing(packing)[0], ctypes.byref(out))
+    return out.value
+
+
+def pack_raw(counts, packing, row_bytes=None):
+    """Integer counts [..., W] -> uint8 [..., row_bytes] in a packed layout (NumPy, on the host: fixtures, tests, tools).
+    Padding pixels of the last group, trailing bits and the bytes up to `row_bytes` (default: the minimum) are zero."""
+    pid, bits, be = _packing(packing)
+    p = np.asarray(counts)
+    if not np.issubdtype(p.dtype, np.integer) or p.ndim < 1:
+        raise TypeError("pack_raw expects integer counts [..., W]")
+    if p.size and (int(p.min()) < 0 or int(p.max()) >= 1 << bits):
+        raise ValueError(f"counts outside the {bits}-bit range")
+    p = p.astype(np.uint32)
+    W = p.shape[-1]
+    if be:
+        stream = ((p[..., None] >> np.arange(bits - 1, -1, -1, dtype=np.uint32)) & 1).astype(np.uint8)
+        rows = np.packbits(stream.reshape(*p.shape[:-1], W * bits), axis=-1)
+    else:
+        G, lb = (2 if bits == 12 else 4), bits - 8
+        g = np.zeros((*p.shape[:-1], -(-W // G) * G), np.uint32)
+        g[..., :W] = p
+        g = g.reshape(*p.shape[:-1], -1, G)
+        low = ((g & ((1 << lb) - 1)) << (lb * np.arange(G, dtype=np.uint32))).sum(axis=-1, dtype=np.uint32)
+        low = (low[..., None] >> (8 * np.arange(G * lb // 8, dtype=np.uint32))) & 255  # little-endian
+        rows = np.concatenate([g >> lb, low], axis=-1).astype(np.uint8).reshape(*p.shape[:-1], -1)
+    need = packed_row_bytes(W, pid)
+    assert rows.shape[-1] == need, (rows.shape, need)
+    if row_bytes is None or int(row_bytes) == need:
+        return np.ascontiguousarray(rows)
+    if int(row_bytes) < need:
+        raise ValueError(f"row_bytes {row_bytes} < {need}, the bytes of {W} pixels")
+    out = np.zeros((*rows.shape[:-1], int(row_bytes)), np.uint8)
+    out[..., :need] = rows
+    return out
+
+
+def unpack_raw(packed, width, packing):
+    """uint8 [..., row_bytes] -> uint16 counts [..., width]: the restated reference of the layouts (NumPy, host)."""
+    pid, bits, be = _packing(packing)
+    b = np.asarray(packed)
+    need = packed_row_bytes(width, pid)
+    if b.dtype != np.uint8 or b.ndim < 1 or b.shape[-1] < need:
+        raise ValueError(f"unpack_raw expects uint8 [..., >= {need}] for {width} pixels")
+    b = b[..., :need]
+    if be:
+        stream = np.unpackbits(b, axis=-1)[..., :width * bits].reshape(*b.shape[:-1], width, bits)
+        p = (stream.astype(np.uint32) << np.arange(bits - 1, -1, -1, dtype=np.uint32)).sum(axis=-1, dtype=np.uint32)
+    else:
+        G, lb = (2 if bits == 12 else 4), bits - 8
+        g = b.reshape(*b.shape[:-1], -1, G + G * lb // 8).astype(np.uint32)
+        low = (g[..., G:] << (8 * np.arange(G * lb // 8, dtype=np.uint32))).sum(axis=-1, dtype=np.uint32)
+        p = (g[..., :G] << lb) | ((low[..., None] >> (lb * np.arange(G, dtype=np.uint32))) & ((1 << lb) - 1))
+        p = p.reshape(*b.shape[:-1], -1)[..., :width]
+    return p.astype(np.uint16)
+
+
+def packed_width(raw_norm, frame):
+    """Image width of a 2-D uint8 frame that config.hip.raw_norm declares packed; None for any other frame (the decision
+    of BurstPipeline._ingest and graph.HostBurstRunner).  ValueError for a packing without a usable width."""
+    if raw_norm is None or raw_norm.get("packing", None) is None or frame.dtype != torch.uint8 or frame.dim() != 2:
+        return None
+    if raw_norm.get("width", None) is None:
+        raise ValueError("config.hip.raw_norm: 'packing' needs 'width', the pixels per row of the packed frames")
+    width = int(raw_norm["width"])
+    if width <= 0 or frame.shape[1] < packed_row_bytes(width, raw_norm["packing"]):
+        raise ValueError(f"config.hip.raw_norm: 'width' {width} as {raw_norm['packing']} needs rows of "
+                         f"{packed_row_bytes(max(width, 1), raw_norm['packing'])} bytes, the frames have {frame.shape[1]}")
+    return width
+
+
+def infer_width(row_bytes, packing):
+    """The width whose packed rows are exactly `row_bytes` long with no padding pixel or bit, or None."""
+    _, bits, be = _packing(packing)
+    per, px = (bits, 8) if be else ((3, 2) if bits == 12 else (bits // 2, 4))  # `per` bytes hold `px` pixels
+    return row_bytes * px // per if row_bytes > 0 and (row_bytes * px) % per == 0 else None
+
+
+def normalize_packed(raw_u8, width, packing, black_levels, white_level, white_balance, cfa_pattern, device=None):
+    """Packed counts uint8 [n, H, row_bytes] (or [H, row_bytes]) -> float32 GPU tensor [n, H, width] (or [H, width]):
+    normalize_burst() of the unpacked counts, bit for bit, without unpacking them on the host (hhsr_normalize_raw_packed).
+    Host data is uploaded as it is on the current stream; rows may be longer than packed_row_bytes(width, packing)."""
+    dev = device or torch.device("cuda", torch.cuda.current_device())
+    pid = _packing(packing)[0]
+    arr = raw_u8 if isinstance(raw_u8, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(raw_u8))
+    if arr.dtype != torch.uint8:
+        raise TypeError("normalize_packed expects the packed bytes as uint8 (got %s)" % arr.dtype)
+    squeeze = arr.dim() == 2
+    if squeeze:
+        arr = arr[None]
+    if arr.dim() != 3:
+        raise ValueError("raw must be [H, row_bytes] or [n, H, row_bytes]")
+    arr = arr.contiguous().to(dev, non_blocking=True)  # current stream; does not block the host for pinned memory
+    n, H, row_bytes = arr.shape
+    out = torch.empty((n, H, int(width)), dtype=torch.float32, device=dev)
+    bl = [float(v) for v in list(black_levels)[:3]]
+    wb = [float(v) for v in list(white_balance)[:3]]
+    if len(bl) < 3 or len(wb) < 3:
+        raise ValueError("black_levels and white_balance need one entry per colour (R, G, B)")
+    _lib.call("hhsr_normalize_raw_packed", _lib.ptr(arr), n, H, int(width), row_bytes, H * row_bytes, pid,
+              _lib.cfa_bytes(cfa_pattern), _lib.doubles(bl), float(white_level), _lib.doubles(wb), _lib.ptr(out),
+              _lib.stream())
     return out[0] if squeeze else out
 
 

@@ -417,6 +417,46 @@ int hhsr_normalize_raw_u16(const uint16_t* raw, int n_frames, int H, int W, int 
                            const double* black_levels, double white_level, const double* white_balance,
                            float* out, void* stream);
 
+/* Packed sensor counts uint8 -> the same normalised float32 [n_frames][H][W], without widening them to uint16 on the
+ * host first.  No counterpart in the reference (rawpy unpacks on the CPU).  p is a B-bit count, b the bytes of a group:
+ *   HHSR_PACK_MIPI10  MIPI CSI-2 RAW10, groups of 4 pixels in 5 bytes:  b[i] = p[i] >> 2 (i < 4),
+ *                     b[4] = (p[0] & 3) | (p[1] & 3) << 2 | (p[2] & 3) << 4 | (p[3] & 3) << 6;      row: 5 ceil(W / 4) bytes
+ *   HHSR_PACK_MIPI12  RAW12, groups of 2 pixels in 3 bytes:  b[i] = p[i] >> 4 (i < 2),
+ *                     b[2] = (p[0] & 15) | (p[1] & 15) << 4;                                       row: 3 ceil(W / 2) bytes
+ *   HHSR_PACK_MIPI14  RAW14, groups of 4 pixels in 7 bytes:  b[i] = p[i] >> 6 (i < 4), then the 24-bit value
+ *                     (p[0] & 63) | (p[1] & 63) << 6 | (p[2] & 63) << 12 | (p[3] & 63) << 18 in b[4], b[5], b[6],
+ *                     least significant byte first;                                                row: 7 ceil(W / 4) bytes
+ *   HHSR_PACK_BE10 / _BE12 / _BE14  uncompressed TIFF / DNG, BitsPerSample B, FillOrder 1: the row is ONE bit stream,
+ *                     pixel x is its bits [x B, (x + 1) B) counted from the most significant bit of byte 0, most
+ *                     significant bit of the count first; every row starts on a byte.               row: ceil(W B / 8) bytes
+ *   e.g. the 10-bit counts 3FF 000 155 2AA 001 are  FF 00 55 AA 93 | 00 00 00 00 01  as MIPI10 (the second group's three
+ *   padding pixels 0) and  FF C0 05 56 AA 00 40  as BE10.
+ * Row y of frame n starts at raw + n * frame_bytes + y * row_bytes (frame_bytes is not read when n_frames == 1); out is
+ * compact.  v = (float32(p) - black[c]) / (white - black[c]) * (wb[c] / wb[1]) with the constants cast as in
+ * hhsr_normalize_raw_u16 and no contraction: bit-identical to that entry point on the unpacked counts.  The padding
+ * pixels of a row's last group, the bits and bytes behind its last pixel and the bytes between rows and frames are not
+ * interpreted (bytes behind the last group / the last bit's byte are not read); nothing outside out[0 .. n H W) is
+ * written.  raw, row_bytes and frame_bytes need no alignment and the result does not depend on theirs: a thread
+ * converts 16 pixels — B / 2 dwords — with dword loads where its row starts on a dword, byte by byte otherwise and for
+ * the last W % 16 pixels of a row.  out is 16-byte aligned.  The fast path (measured: profiles/packed_raw.txt) needs
+ * BOTH every row on a dword — raw, row_bytes and frame_bytes multiples of 4; the minimal row_bytes is not one at every
+ * width, e.g. 5005 bytes for 4004 MIPI10 pixels: pad the rows — AND W % 4 == 0, with which the float4 stores of a
+ * workgroup are contiguous.  Any other row is read byte by byte and any other W stored pixel by pixel, 64 bytes apart
+ * from lane to lane: the same bits, several times the time.  Error -1: a null pointer, an unknown packing, n_frames, H
+ * or W <= 0, n_frames or H > 65535, W > INT32_MAX - 4096, row_bytes below the table's value, frame_bytes < H row_bytes (n_frames > 1),
+ * cfa[k] > 2, white_level == black_levels[c], white_balance[1] == 0, a misaligned out.
+ * hhsr_packed_row_bytes is host-only (no HIP call): the table's row bytes; error -1 for W <= 0 or an unknown packing. */
+#define HHSR_PACK_MIPI10 1
+#define HHSR_PACK_MIPI12 2
+#define HHSR_PACK_MIPI14 3
+#define HHSR_PACK_BE10 4
+#define HHSR_PACK_BE12 5
+#define HHSR_PACK_BE14 6
+int hhsr_normalize_raw_packed(const uint8_t* raw, int n_frames, int H, int W, int64_t row_bytes, int64_t frame_bytes,
+                              int packing, const uint8_t cfa[4], const double* black_levels, double white_level,
+                              const double* white_balance, float* out, void* stream);
+int hhsr_packed_row_bytes(int W, int packing, int64_t* bytes_out);
+
 /* ---- after the path: frame-count denoisers, postprocess, orientation — on the device -------------
  * hhsr_frame_count_denoise: utils_image.py:174-309.  image / out float32 [H][W][3] (the merged image), acc_r float32
  * [ah][aw] (accumulated robustness).  kind 0 = median (strength_max = radius_max <= 7: the reference's 16 x 16 sample
