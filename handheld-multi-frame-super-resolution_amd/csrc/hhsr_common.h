@@ -104,7 +104,9 @@ __device__ __forceinline__ int wave_argmin_first(float cost, int idx, float* min
 
 // XCD-aware workgroup order.  The dispatcher places workgroup b on XCD b % 8 (observed; used for locality
 // only, never for correctness): neighbouring workgroups, which share tile halos, land on different XCDs and
-// each 4 MB L2 fetches the halo again.  This bijection gives every XCD one contiguous range of logical ids.
+// each 4 MB L2 fetches the halo again.  Give every XCD one contiguous band of tile rows so that the heavily
+// overlapping windows of neighbouring tiles hit the same 4 MB L2 instead of being fetched once per XCD.
+// Bijection: XCD x owns ids {b : b % 8 == x} -> contiguous logical ids [start_x, start_x + count_x).
 __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
     const int xcd = bid & 7, loc = bid >> 3, q = nblk >> 3, rem = nblk & 7;
     return xcd * q + min(xcd, rem) + loc;

@@ -1,21 +1,15 @@
-// Internal header of the merge translation units (hhsr_merge*.hip): the arithmetic of Alg. 4 / Alg. 11 as device
-// functions, the launch arguments and the per-family launchers.  Kernel families, one translation unit each:
+// Internal header of the merge translation units (hhsr_merge*.hip).  Kernel families, one translation unit each:
 //   hhsr_merge.hip        C ABI + kernel choice; per-pixel kernels (k_accumulate, k_accumulate_ref, k_merge_burst: any
 //                         scale, float64 validation mode) and the border bands (k_merge_border, _wave)
 //   hhsr_merge_tile.hip   first-generation LDS tile kernels: k_merge_burst_tile (integer scales), k_merge_burst_quad (x2;
 //                         `mode: grey`)
 //   hhsr_merge_x2.hip     k_merge_x2: x2, one wave per Bayer parity class (the headline configuration's kernel)
 //   hhsr_merge_xs.hip     k_merge_xs<3>: the same design with S x S sub-pixels per thread (x3)
+// What they share, in this order: the launch arguments; the arithmetic of Alg. 4 / Alg. 11 per output pixel (comp_contrib,
+// frame_geom, taps_accum, comp_accum_fast, ref_accum_fast, ref_contrib, merge_pixel); the constants of the
+// first-generation tile kernels and quad_tile_body; the constants, LDS access helpers and per-frame pieces of the
+// wave-per-parity-class kernels; the host helpers and the per-family launchers.
 //
-//
-// One thread per high-resolution output pixel, 64x4 pixel workgroups (a wave64 covers 64 consecutive
-// pixels of one output row, so the [sH][sW][3] accumulators are read/written as contiguous 768-byte
-// runs).  Two entry shapes:
-//   hhsr_accumulate / hhsr_accumulate_ref   per-frame read-modify-write of num/den, the reference's
-//                                           operator API (2 x 12 S P bytes of accumulator traffic per frame)
-//   hhsr_merge_burst                        loops over all resident frames with the accumulators in
-//                                           registers and writes the output once: the accumulator
-//                                           traffic drops from 48 S P bytes per frame to 12-24 S P per burst.
 // Arithmetic follows the reference's Numba typing: coordinates, covariance
 // interpolation and weights are float64, the per-pixel val/acc sums are float32 rounded after every
 // tap.  `WT` selects the type of the weight chain: double = the reference's typing (validation mode,
@@ -24,6 +18,7 @@
 #include "hhsr_common.h"
 #include <type_traits>
 
+// ---- launch arguments --------------------------------------------------------------------------------------------------
 struct Cfa4 {
     uint8_t c[4];
 };
@@ -44,6 +39,26 @@ struct Geo {
     double scale;
 };
 
+struct FramePtr {
+    const float* raw;
+    const float2* flow;
+    const float4* cov;
+    const float* r;
+};
+
+struct BurstArgs {
+    FramePtr f[HHSR_MAX_FRAMES];
+    int n;
+    const float* ref_raw;
+    const float4* ref_cov;
+    int flags;
+    float* acc_r;  // optional [H][W]: sum of the frames' robustness (integer scales only)
+    int iscale;    // (int)scale (integer scales: accumulated robustness ownership, tile window sizes)
+    float* cls;    // chained x2 launches (HHSR_MERGE_STORE_CLASSES / _LOAD_CLASSES): per tile 33 x 256 floats
+    int first;     // HHSR_MERGE_LOAD_CLASSES: frames [0, first) are already in `cls` for the wave-uniform tiles
+};
+
+// ---- per-pixel arithmetic ----------------------------------------------------------------------------------------------
 // Border pixels.  A colour can be missing from the reference frame's 3x3 window only when that window is centred on
 // the outermost raw row / column; such a pixel's channel sum may then consist of nothing but far-off samples whose
 // weights sit at the float32 denormal limit (or below it).  The reference evaluates those weights in float64 and
@@ -66,12 +81,12 @@ __device__ __forceinline__ float robustness_at(const float* __restrict__ r, cons
     return m;
 }
 
-struct FramePtr {
-    const float* raw;
-    const float2* flow;
-    const float4* cov;
-    const float* r;
-};
+// The HR pixels with hi % s == 0 and hj % s == 0 map one-to-one onto the LR pixels (integer scale s): they
+// carry the accumulated robustness sum_n r_n of "their" LR pixel (super_resolution.py:158-159), which costs
+// no extra HBM traffic here because r is read for the merge anyway.
+__device__ __forceinline__ bool owns_lr_pixel(const BurstArgs& a, int hi, int hj) {
+    return a.acc_r != nullptr && (hi % a.iscale) == 0 && (hj % a.iscale) == 0;
+}
 
 // ---- one comp frame's contribution to HR pixel (hi, hj)  (merge.py:291-434) -----------------------
 template <typename WT, bool ISO>
@@ -456,24 +471,14 @@ __device__ __forceinline__ bool ref_contrib(const float* __restrict__ raw, const
     return overwrite;
 }
 
-// ---- fused burst kernel -------------------------------------------------------------------------------
-struct BurstArgs {
-    FramePtr f[HHSR_MAX_FRAMES];
-    int n;
-    const float* ref_raw;
-    const float4* ref_cov;
-    int flags;
-    float* acc_r;  // optional [H][W]: sum of the frames' robustness (integer scales only)
-    int iscale;    // (int)scale (integer scales: accumulated robustness ownership, tile window sizes)
-    float* cls;    // chained x2 launches (HHSR_MERGE_STORE_CLASSES / _LOAD_CLASSES): per tile 33 x 256 floats
-    int first;     // HHSR_MERGE_LOAD_CLASSES: frames [0, first) are already in `cls` for the wave-uniform tiles
-};
-
-// The HR pixels with hi % s == 0 and hj % s == 0 map one-to-one onto the LR pixels (integer scale s): they
-// carry the accumulated robustness sum_n r_n of "their" LR pixel (super_resolution.py:158-159), which costs
-// no extra HBM traffic here because r is read for the merge anyway.
-__device__ __forceinline__ bool owns_lr_pixel(const BurstArgs& a, int hi, int hj) {
-    return a.acc_r != nullptr && (hi % a.iscale) == 0 && (hj % a.iscale) == 0;
+// The sums of one output pixel leave: num as the quotient (HHSR_MERGE_DIVIDE) or as it is, den only on request.
+__device__ __forceinline__ void store_pixel(const int flags, float* __restrict__ num, float* __restrict__ den, const size_t o,
+                                            const float n3[3], const float d3[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        num[o + k] = (flags & HHSR_MERGE_DIVIDE) ? n3[k] / d3[k] : n3[k];
+        if (flags & HHSR_MERGE_STORE_DEN) den[o + k] = d3[k];
+    }
 }
 
 // All frames + reference frame + normalisation of ONE output pixel, operands from global memory.
@@ -517,20 +522,14 @@ __device__ __forceinline__ void merge_pixel(const BurstArgs& a, const Geo& g, co
         }
     }
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < 3; ++k) {  // (store_pixel written out: the call changes the listing of k_merge_burst / k_merge_border)
         num[o + k] = (a.flags & HHSR_MERGE_DIVIDE) ? n3[k] / d3[k] : n3[k];
         if (a.flags & HHSR_MERGE_STORE_DEN) den[o + k] = d3[k];
     }
 }
 
-
-// ---- fused burst kernel with LDS staging per flow tile ------------------------------------------------
-// For integer scales the HR tile of one flow vector is ts*scale pixels wide (a multiple of 16), so a 16x16
-// HR workgroup aligned to 16 sees ONE flow vector per frame.  Its raw footprint (<= 19x19 pixels) and
-// covariance footprint (<= 12x12 cells) are fetched once per frame with coalesced loads, staged in LDS
-// and read from there by the 9 taps / 4 covariance cells of every pixel: ~3 vector loads per
-// pixel-frame instead of 15 (the un-staged kernel is bound by the L1 request rate, profiles/r01_b).
-// Loads for frame n+1 are issued into registers before the taps of frame n are evaluated.
+// ---- first-generation LDS tile kernels (hhsr_merge_tile.hip): constants ------------------------------------------------
+// (here, not next to the kernels, because quad_tile_body below is built from them)
 constexpr int MT = 16;                  // HR workgroup edge
 constexpr int RWIN = 19, RPITCH = 21;   // raw window: (MT/s + 3) <= 19, odd-ish pitch against bank conflicts
 constexpr int CWIN = 12;                // covariance window edge (<= MT/2 + 3 cells)
@@ -540,8 +539,32 @@ struct TileWin {
     int cx0, cy0;  // covariance window origin
 };
 
+constexpr int QT = 16;              // LR workgroup edge of the x2 / xS kernels (k_merge_burst_quad, k_merge_x2, k_merge_xs)
+constexpr int QWIN = QT + 3;        // raw window of such a tile: 19 x 19 pixels
+constexpr int QCELLS = QT / 2 + 3;  // its covariance window on the Bayer grid: 11 x 11 cells
+constexpr int QRWIN = QT + 4;       // LMIN: the R window, tile + 2-pixel border: 20 x 20 ...
+constexpr int QRPITCH = QRWIN + 1;  // ... and its pitch in the first-generation kernel
+constexpr int CWM = 20;             // covariance window pitch of the monochrome variant (float4 cells)
 
-// ---- x2 variant: one thread = one LR pixel = its 2 x 2 HR pixels ----------------------------------------------
+// Staging slots of a 256-thread workgroup, by thread id TID (independent of the pixel mapping): every thread fetches
+// elements TID and TID + 256 of the QWIN^2 raw window (e0y, e0x; e1y, e1x if has1), cell TID of the CW^2 covariance window
+// (cey, cex if hasc) and, LMIN, elements TID and TID + 256 of the QRWIN^2 R window around the tile at LR origin (lx0, ly0)
+// (m0y, m0x; m1y, m1x if hasm1; moff0 / moff1: their offsets in the frame's map, clamped into the frame; g, lx0 and ly0
+// are the kernel's).  Used by quad_tile_body, k_merge_x2 and k_merge_xs.
+// A macro, not a function: as a function (three forms, profiles/merge_sources.txt) the divisions compile to different
+// instructions, and the kernels' listings are what merge changes are checked against.
+#define HHSR_STAGE_SLOTS(TID, CW, LMIN)                                                                      \
+    const int e0 = TID, e1 = TID + 256;                                                                      \
+    const int e0y = e0 / QWIN, e0x = e0 - e0y * QWIN, e1y = e1 / QWIN, e1x = e1 - e1y * QWIN;                \
+    const int cey = TID / CW, cex = TID - cey * CW;                                                          \
+    const bool has1 = e1 < QWIN * QWIN, hasc = TID < CW * CW;                                                \
+    const int m0y = TID / QRWIN, m0x = TID - m0y * QRWIN;                                                    \
+    const int m1 = TID + 256, m1y = m1 / QRWIN, m1x = m1 - m1y * QRWIN;                                      \
+    const bool hasm1 = LMIN && m1 < QRWIN * QRWIN;                                                           \
+    const int moff0 = clampi(ly0 - 2 + m0y, 0, g.H - 1) * g.W + clampi(lx0 - 2 + m0x, 0, g.W - 1);           \
+    const int moff1 = clampi(ly0 - 2 + m1y, 0, g.H - 1) * g.W + clampi(lx0 - 2 + m1x, 0, g.W - 1);
+
+// ---- quad_tile_body: one thread = one LR pixel = its 2 x 2 HR pixels ---------------------------------------------------
 // At scale 2 the four HR pixels of an LR pixel share the robustness sample, the flow vector, the staged windows
 // and most of the geometry (their centres differ by at most one raw pixel, decided by wave-uniform comparisons
 // of frac(flow) with 0.25 / 0.75).  A 16 x 16 LR workgroup (32 x 32 HR, inside one flow tile for ts % 16 == 0)
@@ -549,26 +572,20 @@ struct TileWin {
 // address arithmetic and the two workgroup barriers are paid once per FOUR output pixels, and every thread owns
 // exactly one accumulated-robustness sample.  Same arithmetic per HR pixel as k_merge_burst_tile (frame_geom /
 // taps_accum are shared), so results are bit-identical to it.
-constexpr int QT = 16;  // LR workgroup edge
-
 // Body of the first-generation x2 kernel: general per-pixel geometry, any window position.  s_raw: >= RWIN * RPITCH
-// floats, s_cov: >= CWIN * CWIN float4, s_R: >= (QT + 4) * (QT + 5) floats (LMIN).
+// floats, s_cov: >= CWIN * CWIN float4, s_R: >= QRWIN * QRPITCH floats (LMIN).  It is in the header because two kernels
+// run it: k_merge_burst_quad as its whole body, k_merge_x2 for its perimeter tiles.
 // MONO (`mode: grey`, merge.py:349-354): one covariance per PIXEL, so the staged covariance window has the raw
 // window's extent (19 x 19 cells at pitch CWM) instead of the Bayer grid's 11 x 11; the all-zero CFA pattern of a
 // monochrome launch routes the four parity classes into channel 0 (classes_to_rgb).
-constexpr int CWM = 20;  // covariance window pitch of the monochrome variant (float4 cells)
 template <bool ISO, bool LMIN, bool MONO = false>
 __device__ __forceinline__ void quad_tile_body(const BurstArgs& a, const Geo& g, const Cfa4 cfa, float* __restrict__ num,
                                                float* __restrict__ den, float* __restrict__ s_raw,
                                                float4* __restrict__ s_cov, float* __restrict__ s_Rf) {
-    float (*s_R)[QT + 4 + 1] = reinterpret_cast<float (*)[QT + 4 + 1]>(s_Rf);
+    float (*s_R)[QRPITCH] = reinterpret_cast<float (*)[QRPITCH]>(s_Rf);
     const int tx = threadIdx.x & (QT - 1), ty = threadIdx.x >> 4;
     const int nbx = gridDim.x, nblk = gridDim.x * gridDim.y;
-    int bid = blockIdx.y * nbx + blockIdx.x;
-    {   // XCD-aware tile order, see k_merge_burst_tile
-        const int xcd = bid & 7, loc = bid >> 3, q = nblk >> 3, rem = nblk & 7;
-        bid = xcd * q + min(xcd, rem) + loc;
-    }
+    const int bid = xcd_remap(blockIdx.y * nbx + blockIdx.x, nblk);
     const int lx0 = (bid % nbx) * QT, ly0 = (g.row0 >> 1) + (bid / nbx) * QT;  // LR origin of the workgroup
     const int lx = lx0 + tx, ly = ly0 + ty;
     const bool live = lx < g.W && 2 * ly < g.row1;
@@ -588,23 +605,14 @@ __device__ __forceinline__ void quad_tile_body(const BurstArgs& a, const Geo& g,
     }
     float racc = 0.f;
 
-    constexpr int rwin = QT + 3, cwin = MONO ? QT + 3 : QT / 2 + 3;  // 19 raw pixels, 11 (monochrome: 19) covariance cells
-    constexpr int CP = MONO ? CWM : CWIN;                             // pitch of the staged covariance window
-    static_assert(rwin <= RWIN && cwin <= CP, "window buffers");
-    const int e0 = threadIdx.x, e1 = threadIdx.x + 256;
-    const int e0y = e0 / rwin, e0x = e0 - e0y * rwin, e1y = e1 / rwin, e1x = e1 - e1y * rwin;
-    const int cey = threadIdx.x / cwin, cex = threadIdx.x - cey * cwin;
-    const int ce1 = threadIdx.x + 256, ce1y = ce1 / cwin, ce1x = ce1 - ce1y * cwin;  // (monochrome: 361 cells)
-    const bool has1 = e1 < rwin * rwin, hasc = threadIdx.x < cwin * cwin, hasc1 = MONO && ce1 < cwin * cwin;
-
+    constexpr int cwin = MONO ? QWIN : QCELLS;  // 11 (monochrome: 19) covariance cells
+    constexpr int CP = MONO ? CWM : CWIN;       // pitch of the staged covariance window
+    static_assert(QWIN <= RWIN && cwin <= CP, "window buffers");
     // LMIN: the frames carry the thresholded map R; r = its 5x5 clamp-border minimum (robustness.py:641-686) is
-    // taken here from a (QT+4)^2 window — the separate local-minimum pass and its 8 B/pixel disappear
-    constexpr int RW = QT + 4;
-    const int m0y = threadIdx.x / RW, m0x = threadIdx.x - m0y * RW;
-    const int m1 = threadIdx.x + 256, m1y = m1 / RW, m1x = m1 - m1y * RW;
-    const bool hasm1 = LMIN && m1 < RW * RW;
-    const int moff0 = clampi(ly0 - 2 + m0y, 0, g.H - 1) * g.W + clampi(lx0 - 2 + m0x, 0, g.W - 1);
-    const int moff1 = clampi(ly0 - 2 + m1y, 0, g.H - 1) * g.W + clampi(lx0 - 2 + m1x, 0, g.W - 1);
+    // taken here from a QRWIN^2 window — the separate local-minimum pass and its 8 B/pixel disappear
+    HHSR_STAGE_SLOTS(threadIdx.x, cwin, LMIN)
+    const int ce1 = threadIdx.x + 256, ce1y = ce1 / cwin, ce1x = ce1 - ce1y * cwin;  // (monochrome: 361 cells)
+    const bool hasc1 = MONO && ce1 < cwin * cwin;
     float pr0 = 0.f, pr1 = 0.f, plr = 0.f, plr1 = 0.f;
     float4 pc = make_float4(0.f, 0.f, 0.f, 0.f), pc1 = pc;
     float2 pfl = make_float2(0.f, 0.f);
@@ -706,17 +714,11 @@ __device__ __forceinline__ void quad_tile_body(const BurstArgs& a, const Geo& g,
             }
             if (a.flags & HHSR_MERGE_DO_REF) ref_accum_fast<ISO>(a.ref_raw, a.ref_cov, g, hi, hj, n4[sa][sb], d4[sa][sb]);
             classes_to_rgb(cfa, n4[sa][sb], d4[sa][sb], n3, d3);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                num[o + k] = (a.flags & HHSR_MERGE_DIVIDE) ? n3[k] / d3[k] : n3[k];
-                if (a.flags & HHSR_MERGE_STORE_DEN) den[o + k] = d3[k];
-            }
+            store_pixel(a.flags, num, den, o, n3, d3);
         }
 }
 
-
-
-// ---- x2, second generation: one WAVE per Bayer parity class --------------------------------------------------------
+// ---- k_merge_x2 / k_merge_xs: one WAVE per Bayer parity class ----------------------------------------------------------
 // Same tile as k_merge_burst_quad (16 x 16 LR = 32 x 32 HR pixels inside one flow tile, one thread per LR pixel = its
 // 2 x 2 HR pixels), but wave w of the workgroup owns the 8 x 8 LR pixels of ONE parity class (row parity w >> 1, column
 // parity w & 1).  With the flow shared by the tile, everything that depends on sub-pixel position and parity is then
@@ -740,17 +742,9 @@ __device__ __forceinline__ void quad_tile_body(const BurstArgs& a, const Geo& g,
 // reference frame through run-time selects instead of a compile-time variant of the frame code (160 VGPRs: 3.97 vs 3.54
 // ms); per-frame geometry once per workgroup through LDS; 3 + 3 channel accumulators instead of 4 + 4 parity classes;
 // k_merge_xs: EDGE frames through the uniform code with masks, the LDS reads of sub-pixel q + 1 issued before the taps of q.
-#ifndef HHSR_XS_OCC
-#define HHSR_XS_OCC 2  // k_merge_xs<3>: 54 accumulators per thread; 3 waves per SIMD (168 VGPRs) spills 50 dwords
-#endif
-#ifndef HHSR_X2_OCC
-#define HHSR_X2_OCC 4  // waves per SIMD the register allocation of k_merge_x2 is held to (122 VGPRs; A/B: 3 = 4; 5 spills: 6.9 ms)
-#endif
 constexpr int X2_RP = 24;   // raw / R window pitch in floats: rows are read with stride 2 -> 48 dwords = 16 (mod 32) banks
 constexpr int X2_CP = 24;   // covariance window pitch in float4: 96 dwords = 32 (mod 64) banks for ds_read_b128
-constexpr int X2_OP = 100;  // output tile pitch in floats (96 + 4: rows stay 16-byte aligned)
 constexpr float X2_KEXP = -0.72134752044448170368f;  // -0.5 * log2(e)
-constexpr int X2_WIN = QT + 3;                        // 19 x 19 raw window
 
 // LDS reads as exactly the instruction written: the compiler narrows a float4 whose .z is unused into ds_read2_b32
 // (cells are 4 dwords apart: 4-way bank conflicts), narrows a half-used pair to a stride-2 ds_read_b32 (2-way) and
@@ -816,6 +810,35 @@ __device__ __forceinline__ X2Axis x2_ref_axis(int l0, int p) {
     return u;
 }
 
+// Covariance at a sub-pixel, cxx / cxy / cyy: its four staged cells blended with the bilinear fractions (GX, GY) ...
+#define HHSR_COV_BLEND(C00, C01, C10, C11, GX, GY)                                                     \
+    const float gx = GX, gy = GY;                                                                      \
+    const float w11 = gx * gy, w01 = gx - w11, w10 = gy - w11, w00 = (1.f - gx) - w10;                 \
+    const float cxx = fmaf(w11, C11.x, fmaf(w10, C10.x, fmaf(w01, C01.x, w00 * C00.x)));               \
+    const float cxy = fmaf(w11, C11.y, fmaf(w10, C10.y, fmaf(w01, C01.y, w00 * C00.y)));               \
+    const float cyy = fmaf(w11, C11.w, fmaf(w10, C10.w, fmaf(w01, C01.w, w00 * C00.w)));
+// ... and its inverse as the coefficients ixx / ixy / iyy of the taps' exponent (X2_KEXP folded in); leaves det.
+// (Macros: as functions they change k_merge_xs' listing, profiles/merge_sources.txt; two, so that k_merge_x2's
+// `//@ cov_blend` and `//@ inverse` regions stay apart.)
+#define HHSR_COV_INVERSE()                                                                             \
+    const float det = fmaf(cxx, cyy, -(cxy * cxy));                                                    \
+    const float s1 = __builtin_amdgcn_rcpf(det) * X2_KEXP;                                             \
+    ixx = s1 * cyy;                                                                                    \
+    ixy = (-2.f * s1) * cxy;                                                                           \
+    iyy = s1 * cxx;
+
+// One frame's tap sums of sub-pixel (sa, sb), sv / sd[tap-offset parity], into its R, G, B accumulators nacc / dacc with the
+// robustness factor R; (RA, RB) = the tap parity the red samples sit at, blue diagonally opposite, the two greens summed.
+#define HHSR_FOLD3(R, RA, RB)                                                          \
+    {                                                                                  \
+        nacc[sa][sb][0] = fmaf(R, sv[RA][RB], nacc[sa][sb][0]);                        \
+        dacc[sa][sb][0] = fmaf(R, sd[RA][RB], dacc[sa][sb][0]);                        \
+        nacc[sa][sb][1] = fmaf(R, sv[RA ^ 1][RB] + sv[RA][RB ^ 1], nacc[sa][sb][1]);   \
+        dacc[sa][sb][1] = fmaf(R, sd[RA ^ 1][RB] + sd[RA][RB ^ 1], dacc[sa][sb][1]);   \
+        nacc[sa][sb][2] = fmaf(R, sv[RA ^ 1][RB ^ 1], nacc[sa][sb][2]);                \
+        dacc[sa][sb][2] = fmaf(R, sd[RA ^ 1][RB ^ 1], dacc[sa][sb][2]);                \
+    }
+
 // the R, G, B sums of one sub-pixel from its NC accumulators (3: channels already; 4: parity classes -> channels)
 template <int NC>
 __device__ __forceinline__ void xs_rgb(const Cfa4 cfa, const float* nsub, const float* dsub, float n3[3], float d3[3]) {
@@ -833,14 +856,45 @@ __device__ __forceinline__ void xs_rgb(const Cfa4 cfa, const float* nsub, const 
     }
 }
 
+// HHSR_MERGE_LOAD_ACC epilogue of the wave-per-parity-class kernels (bursts longer than one launch, multi-GPU finish): the
+// S x S output pixels of LR pixel (ly, lx) are added to what an earlier launch left in num / den, pixel by pixel; the
+// border bands keep their input for k_merge_border.  Reads a, g, cfa, num, den, ly, lx, nacc, dacc and NC of the kernel.
+// (A macro: as a function, two forms, it changes both kernels' listings; profiles/merge_sources.txt.)
+#define HHSR_ADD_TO_OUTPUT(S)                                                               \
+    _Pragma("unroll")                                                                       \
+    for (int sa = 0; sa < S; ++sa)                                                          \
+    _Pragma("unroll")                                                                       \
+        for (int sb = 0; sb < S; ++sb) {                                                    \
+            const int hi = S * ly + sa, hj = S * lx + sb;                                   \
+            if (border_pixel(g, hi, hj)) continue;                                          \
+            const size_t o = ((size_t)(hi - g.row0) * g.sW + hj) * 3;                       \
+            float n3[3], d3[3];                                                             \
+            xs_rgb<NC>(cfa, nacc[sa][sb], dacc[sa][sb], n3, d3);                            \
+    _Pragma("unroll")                                                                       \
+            for (int k = 0; k < 3; ++k) {                                                   \
+                const float nk = num[o + k] + n3[k], dk = den[o + k] + d3[k];               \
+                num[o + k] = (a.flags & HHSR_MERGE_DIVIDE) ? nk / dk : nk;                  \
+                if (a.flags & HHSR_MERGE_STORE_DEN) den[o + k] = dk;                        \
+            }                                                                               \
+        }
 
+// ---- host helpers; launchers of the kernel families (defined next to their kernels) ------------------------------------
 static inline bool cfa_is_bayer(const Cfa4& c) {  // red (0) and blue (2) on one diagonal, green (1) on the other
     for (int k = 0; k < 4; ++k)
         if (c.c[k] == 0) return c.c[3 - k] == 2 && c.c[k ^ 1] == 1 && c.c[k ^ 2] == 1;
     return false;
 }
 
-// ---- launchers of the kernel families (defined next to their kernels) ---------------------------------------------------
+// Run-time flags -> template arguments: fn gets one std::true_type / std::false_type per flag, in their order.  Every
+// combination is instantiated, the first flag varying slowest: that is the order of the kernels in the listing.
+template <class Fn>
+static inline void with_bool_tags(Fn fn) { fn(); }
+template <class Fn, class... Flags>
+static inline void with_bool_tags(Fn fn, bool flag, Flags... flags) {
+    if (flag) with_bool_tags([&](auto... tags) { fn(std::true_type{}, tags...); }, flags...);
+    else with_bool_tags([&](auto... tags) { fn(std::false_type{}, tags...); }, flags...);
+}
+
 void hhsr_launch_merge_tile(bool p2, bool iso, dim3 grid, hipStream_t s, const BurstArgs& a, const Geo& g, const Cfa4& c,
                             float* num, float* den);
 void hhsr_launch_merge_quad(bool iso, bool lmin, bool mono, dim3 grid, hipStream_t s, const BurstArgs& a, const Geo& g,

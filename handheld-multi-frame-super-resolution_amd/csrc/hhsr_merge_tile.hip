@@ -1,18 +1,23 @@
 // First-generation LDS tile kernels of the fused burst merge (see hhsr_merge.h for the family overview).
 #include "hhsr_merge.h"
 
+// ---- fused burst kernel with LDS staging per flow tile ------------------------------------------------
+// For integer scales the HR tile of one flow vector is ts*scale pixels wide (a multiple of 16), so a 16x16
+// HR workgroup aligned to 16 sees ONE flow vector per frame.  Its raw footprint (<= 19x19 pixels) and
+// covariance footprint (<= 12x12 cells) are fetched once per frame with coalesced loads, staged in LDS
+// and read from there by the 9 taps / 4 covariance cells of every pixel: ~3 vector loads per
+// pixel-frame instead of 15 (the un-staged kernel is bound by the L1 request rate, profiles/r01_b).
+// Loads for frame n+1 are issued into registers before the taps of frame n are evaluated.
 template <int GEOM, bool ISO>
 __global__ void __launch_bounds__(256) k_merge_burst_tile(BurstArgs a, Geo g, Cfa4 cfa, float* __restrict__ num,
                                                            float* __restrict__ den) {
     __shared__ float s_raw[RWIN * RPITCH];
     __shared__ float4 s_cov[CWIN * CWIN];
     const int tx = threadIdx.x & (MT - 1), ty = threadIdx.x >> 4;
-    // XCD-aware workgroup -> tile mapping: the dispatcher places workgroup b on XCD b % 8 (observed, used for
-    // L2 locality only).  Give every XCD one contiguous band of tile rows so that the heavily overlapping
-    // windows of neighbouring tiles hit the same 4 MB L2 instead of being fetched once per XCD.
     const int nbx = gridDim.x, nblk = gridDim.x * gridDim.y;
     int bid = blockIdx.y * nbx + blockIdx.x;
-    {   // bijection: XCD x owns ids {b : b % 8 == x} -> contiguous tiles [start_x, start_x + count_x)
+    {   // xcd_remap(bid, nblk) written out: the call swaps the operands of one s_mul_i32 in this kernel's listing, in every
+        // spelling tried (profiles/merge_sources.txt), and the listing is what merge changes are checked against
         const int xcd = bid & 7, loc = bid >> 3, q = nblk >> 3, rem = nblk & 7;
         bid = xcd * q + min(xcd, rem) + loc;
     }
@@ -27,7 +32,8 @@ __global__ void __launch_bounds__(256) k_merge_burst_tile(BurstArgs a, Geo g, Cf
     float racc = 0.f;  // sum of this pixel's robustness over the frames
 
     // staging slots of this thread: raw window elements tid and tid+256, covariance element tid.  Only the
-    // (MT/s + 3)^2 raw pixels and (MT/(2s) + 3)^2 covariance cells the taps can reach are fetched.
+    // (MT/s + 3)^2 raw pixels and (MT/(2s) + 3)^2 covariance cells the taps can reach are fetched.  (Run-time window
+    // edges; the x2 / xS kernels' compile-time form of these lines is HHSR_STAGE_SLOTS.)
     const int rwin = min(RWIN, (MT + a.iscale - 1) / a.iscale + 3);
     const int cwin = min(CWIN, (MT + 2 * a.iscale - 1) / (2 * a.iscale) + 3);
     const int e0 = threadIdx.x, e1 = threadIdx.x + 256;
@@ -114,11 +120,7 @@ __global__ void __launch_bounds__(256) k_merge_burst_tile(BurstArgs a, Geo g, Cf
     }
     if (a.flags & HHSR_MERGE_DO_REF) ref_accum_fast<ISO>(a.ref_raw, a.ref_cov, g, hi, hj, n4, d4);
     classes_to_rgb(cfa, n4, d4, n3, d3);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        num[o + k] = (a.flags & HHSR_MERGE_DIVIDE) ? n3[k] / d3[k] : n3[k];
-        if (a.flags & HHSR_MERGE_STORE_DEN) den[o + k] = d3[k];
-    }
+    store_pixel(a.flags, num, den, o, n3, d3);
 }
 
 
@@ -126,30 +128,21 @@ template <bool ISO, bool LMIN, bool MONO = false>
 __global__ void __launch_bounds__(256) k_merge_burst_quad(BurstArgs a, Geo g, Cfa4 cfa, float* __restrict__ num,
                                                            float* __restrict__ den) {
     __shared__ float s_raw[RWIN * RPITCH];
-    __shared__ float4 s_cov[MONO ? (QT + 3) * CWM : CWIN * CWIN];
-    __shared__ float s_R[LMIN ? (QT + 4) * (QT + 4 + 1) : 1];  // LMIN: un-filtered robustness of the tile + 2-pixel border
+    __shared__ float4 s_cov[MONO ? QWIN * CWM : CWIN * CWIN];
+    __shared__ float s_R[LMIN ? QRWIN * QRPITCH : 1];  // LMIN: un-filtered robustness of the tile + 2-pixel border
     quad_tile_body<ISO, LMIN, MONO>(a, g, cfa, num, den, s_raw, s_cov, s_R);
 }
 
 void hhsr_launch_merge_tile(bool p2, bool iso, dim3 grid, hipStream_t s, const BurstArgs& a, const Geo& g, const Cfa4& c,
                             float* num, float* den) {
-    const dim3 block(256);
-#define HHSR_MT(GEOM, ISO) hipLaunchKernelGGL((k_merge_burst_tile<GEOM, ISO>), grid, block, 0, s, a, g, c, num, den)
-    if (p2) { if (iso) HHSR_MT(GEOM_P2, true); else HHSR_MT(GEOM_P2, false); }
-    else { if (iso) HHSR_MT(GEOM_F64, true); else HHSR_MT(GEOM_F64, false); }
-#undef HHSR_MT
+    with_bool_tags([&](auto P2, auto ISO) {
+        hipLaunchKernelGGL((k_merge_burst_tile<P2.value ? GEOM_P2 : GEOM_F64, ISO.value>), grid, dim3(256), 0, s, a, g, c, num, den);
+    }, p2, iso);
 }
 
 void hhsr_launch_merge_quad(bool iso, bool lmin, bool mono, dim3 grid, hipStream_t s, const BurstArgs& a, const Geo& g,
                             const Cfa4& c, float* num, float* den) {
-    const dim3 block(256);
-#define HHSR_MQ(ISO, LMIN, MONO) hipLaunchKernelGGL((k_merge_burst_quad<ISO, LMIN, MONO>), grid, block, 0, s, a, g, c, num, den)
-    if (mono) {
-        if (lmin) { if (iso) HHSR_MQ(true, true, true); else HHSR_MQ(false, true, true); }
-        else { if (iso) HHSR_MQ(true, false, true); else HHSR_MQ(false, false, true); }
-    } else {
-        if (lmin) { if (iso) HHSR_MQ(true, true, false); else HHSR_MQ(false, true, false); }
-        else { if (iso) HHSR_MQ(true, false, false); else HHSR_MQ(false, false, false); }
-    }
-#undef HHSR_MQ
+    with_bool_tags([&](auto MONO, auto LMIN, auto ISO) {
+        hipLaunchKernelGGL((k_merge_burst_quad<ISO.value, LMIN.value, MONO.value>), grid, dim3(256), 0, s, a, g, c, num, den);
+    }, mono, lmin, iso);
 }

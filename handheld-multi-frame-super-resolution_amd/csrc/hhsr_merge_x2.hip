@@ -1,20 +1,25 @@
 // k_merge_x2: the fused burst merge at x2, one wave per Bayer parity class (see hhsr_merge.h for the family overview and
-// the comment block above the HHSR_X2_* switches there for the design).
+// its wave-per-parity-class section for the design).
 #include "hhsr_merge.h"
 
 // Instruction budget (tools/isa_budget.py): the `//@ name` tags below open the source regions the script attributes the
 // kernel's instructions to (through the line table of a -gline-tables-only build).  -DHHSR_X2_BUDGET (analysis builds only)
 // leaves out the tap arm for non-finite coefficients, which ordinary data never executes.
 
+#ifndef HHSR_X2_OCC
+#define HHSR_X2_OCC 4  // waves per SIMD the register allocation of k_merge_x2 is held to (122 VGPRs; A/B: 3 = 4; 5 spills: 6.9 ms)
+#endif
+constexpr int X2_OP = 100;  // output tile pitch in floats (96 + 4: rows stay 16-byte aligned)
+
 template <bool ISO, bool LMIN>
 __global__ void __launch_bounds__(256, HHSR_X2_OCC) k_merge_x2(BurstArgs a, Geo g, Cfa4 cfa, float* __restrict__ num,
                                                    float* __restrict__ den) {
-    constexpr int NB = 1;  // window buffers (a double-buffered variant with one barrier per frame measured slower: 3.76 vs 3.64 ms, round 2)
-    constexpr int RAWSZ = 20 * X2_RP, COVSZ = CWIN * X2_CP;
-    __shared__ __align__(16) float s_rawA[NB * RAWSZ];              // window[y][x]
-    __shared__ __align__(16) float s_rawB[NB * RAWSZ];              // window[y][x + 1]
-    __shared__ float4 s_cov[NB * COVSZ];
-    __shared__ __align__(16) float s_R[NB * RAWSZ];                 // LMIN: un-filtered robustness, tile + 2-pixel border
+    // one buffer per window (a double-buffered variant with one barrier per frame measured slower: 3.76 vs 3.64 ms, round 2)
+    constexpr int RAWSZ = QRWIN * X2_RP, COVSZ = CWIN * X2_CP;
+    __shared__ __align__(16) float s_rawA[RAWSZ];                   // window[y][x]
+    __shared__ __align__(16) float s_rawB[RAWSZ];                   // window[y][x + 1]
+    __shared__ float4 s_cov[COVSZ];
+    __shared__ __align__(16) float s_R[RAWSZ];                      // LMIN: un-filtered robustness, tile + 2-pixel border
     __shared__ __align__(16) float s_out[32 * X2_OP];
     __shared__ float4 s_geo[(HHSR_MAX_FRAMES + 1) * 8];             // per frame: [axis x, y][parity 0, 1] x 2 quads
     const int tid = threadIdx.x;
@@ -42,7 +47,7 @@ __global__ void __launch_bounds__(256, HHSR_X2_OCC) k_merge_x2(BurstArgs a, Geo 
     if (ok && lane < a.n) {
         const float2 fl = a.f[lane].flow[tile];
         const int ox = x2_comp_org(fl.x, lx0), oy = x2_comp_org(fl.y, ly0);
-        ok = ox >= 0 && ox + X2_WIN <= g.W && oy >= 0 && oy + X2_WIN <= g.H;  // NaN flow: (int) of NaN is checked too
+        ok = ox >= 0 && ox + QWIN <= g.W && oy >= 0 && oy + QWIN <= g.H;  // NaN flow: (int) of NaN is checked too
         ok = ok && fl.x == fl.x && fl.y == fl.y;
     }
     if (!__all(ok)) {  // wave-uniform, identical in the four waves
@@ -103,22 +108,10 @@ __global__ void __launch_bounds__(256, HHSR_X2_OCC) k_merge_x2(BurstArgs a, Geo 
         }
     }
 
-    // staging slots (by thread id, independent of the pixel mapping)
-    constexpr int rwin = X2_WIN, cwin = QT / 2 + 3;  // 19 raw pixels, 11 covariance cells
-    const int e0 = tid, e1 = tid + 256;
-    const int e0y = e0 / rwin, e0x = e0 - e0y * rwin, e1y = e1 / rwin, e1x = e1 - e1y * rwin;
-    const int cey = tid / cwin, cex = tid - cey * cwin;
-    const bool has1 = e1 < rwin * rwin, hasc = tid < cwin * cwin;
-    constexpr int RW = QT + 4;
-    const int m0y = tid / RW, m0x = tid - m0y * RW;
-    const int m1 = tid + 256, m1y = m1 / RW, m1x = m1 - m1y * RW;
-    const bool hasm1 = LMIN && m1 < RW * RW;
-    const int moff0 = clampi(ly0 - 2 + m0y, 0, g.H - 1) * g.W + clampi(lx0 - 2 + m0x, 0, g.W - 1);
-    const int moff1 = clampi(ly0 - 2 + m1y, 0, g.H - 1) * g.W + clampi(lx0 - 2 + m1x, 0, g.W - 1);
+    HHSR_STAGE_SLOTS(tid, QCELLS, LMIN)
     const int nloop = a.n + ((a.flags & HHSR_MERGE_DO_REF) ? 1 : 0);  // the reference frame is the last "frame"
     float pr0 = 0.f, pr1 = 0.f, plr = 0.f, plr1 = 0.f;
     float4 pc = make_float4(0.f, 0.f, 0.f, 0.f);
-    float2 pfl = make_float2(0.f, 0.f);
     // Byte offsets of the staging slots that do not depend on the frame; the frame's window origin is wave-uniform (read
     // back from the geometry table into SGPRs), so a load is ONE v_add_u32 + global_load ... s[base:base+1] — the first
     // version recomputed floor / compare / convert of the flow vector per thread and frame behind a dependent global load of
@@ -143,7 +136,7 @@ __global__ void __launch_bounds__(256, HHSR_X2_OCC) k_merge_x2(BurstArgs a, Geo 
             // Windows that stay inside the cell grid — all but the last tile row / column's — take ONE v_add per thread.
             const int cx0 = ox >> 1, cy0 = oy >> 1;
             unsigned ci;
-            if (cx0 + cwin <= g.gw && cy0 + cwin <= g.gh) {  // (scalar)
+            if (cx0 + QCELLS <= g.gw && cy0 + QCELLS <= g.gh) {  // (scalar)
                 ci = (unsigned)(cy0 * g.gw + cx0) + cinv;
             } else {
                 asm volatile("; clamped cells");  // (keeps the arm a branch)
@@ -166,25 +159,23 @@ __global__ void __launch_bounds__(256, HHSR_X2_OCC) k_merge_x2(BurstArgs a, Geo 
     const int cbase = li * X2_CP + lj;
     const int tyrp = ty * X2_RP + 2 * lj;
 
-    // write the prefetched registers of one frame into window buffer `bo`; returns that frame's flow / robustness
-    float2 sfl = make_float2(0.f, 0.f);
+    // write the prefetched registers of one frame into the windows; leaves that frame's robustness in sr
     float sr = 0.f;
     //@ outside
-    auto stage = [&](int n, int bo) {
+    auto stage = [&](int n) {
         //@ staging
         const bool isref = n >= a.n;
-        s_rawA[bo * RAWSZ + e0y * X2_RP + e0x] = pr0;
-        if (e0x > 0) s_rawB[bo * RAWSZ + e0y * X2_RP + e0x - 1] = pr0;
+        s_rawA[e0y * X2_RP + e0x] = pr0;
+        if (e0x > 0) s_rawB[e0y * X2_RP + e0x - 1] = pr0;
         if (has1) {
-            s_rawA[bo * RAWSZ + e1y * X2_RP + e1x] = pr1;
-            if (e1x > 0) s_rawB[bo * RAWSZ + e1y * X2_RP + e1x - 1] = pr1;
+            s_rawA[e1y * X2_RP + e1x] = pr1;
+            if (e1x > 0) s_rawB[e1y * X2_RP + e1x - 1] = pr1;
         }
-        if (!ISO && hasc) s_cov[bo * COVSZ + cey * X2_CP + cex] = pc;
+        if (!ISO && hasc) s_cov[cey * X2_CP + cex] = pc;
         if (LMIN && !isref) {
-            s_R[bo * RAWSZ + m0y * X2_RP + m0x] = plr;
-            if (hasm1) s_R[bo * RAWSZ + m1y * X2_RP + m1x] = plr1;
+            s_R[m0y * X2_RP + m0x] = plr;
+            if (hasm1) s_R[m1y * X2_RP + m1x] = plr1;
         }
-        sfl = pfl;
         sr = isref ? 1.f : plr;
     };
     // One frame of taps.  ISREF is a compile-time flag (the reference frame runs the same code with its own uniform
@@ -192,8 +183,8 @@ __global__ void __launch_bounds__(256, HHSR_X2_OCC) k_merge_x2(BurstArgs a, Geo 
     // and on gfx950 v_cndmask / v_min / v_cmp / v_floor / v_cvt issue at HALF the v_fma rate, v_exp / v_rcp at a quarter
     // (tools/ubench/valu_rate.hip) — the kernel is VALU-bound, so instruction classes are what to count.
     //@ outside
-    auto frame = [&](auto isref_c, const bool isref_rt, const float2 fl, float local_r, const int bo, const int n) {
-        const bool isref = isref_rt;  // (as a compile-time variant of the frame code: 160 VGPRs, 3.97 vs 3.54 ms — round 2)
+    auto frame = [&](const int n, float local_r) {
+        const bool isref = n >= a.n;  // (as a compile-time variant of the frame code: 160 VGPRs, 3.97 vs 3.54 ms — round 2)
         // the same flag as an opaque scalar INTEGER: as a bool the compiler carries it between blocks as a lane mask and
         // rebuilds the branch condition with v_cndmask + v_cmp per use
         int isref_s = __builtin_amdgcn_readfirstlane(n) - __builtin_amdgcn_readfirstlane(a.n);  // >= 0: the reference frame
@@ -207,8 +198,8 @@ __global__ void __launch_bounds__(256, HHSR_X2_OCC) k_merge_x2(BurstArgs a, Geo 
             if (px) {  // (uniform branch instead of a select per row)
 #pragma unroll
                 for (int r = 0; r < 5; ++r) {
-                    const float2 v01 = lds_pair(rbase + bo * RAWSZ + r * X2_RP), v23 = lds_pair(rbase + bo * RAWSZ + r * X2_RP + 2);
-                    const float2 v45 = lds_pair(rbase + bo * RAWSZ + r * X2_RP + 4);
+                    const float2 v01 = lds_pair(rbase + r * X2_RP), v23 = lds_pair(rbase + r * X2_RP + 2);
+                    const float2 v45 = lds_pair(rbase + r * X2_RP + 4);
                     const unsigned rm = min(min(__float_as_uint(v01.y), __float_as_uint(v23.x)),
                                    min(__float_as_uint(v23.y), min(__float_as_uint(v45.x), __float_as_uint(v45.y))));
                     m = r ? min(m, rm) : rm;
@@ -216,8 +207,8 @@ __global__ void __launch_bounds__(256, HHSR_X2_OCC) k_merge_x2(BurstArgs a, Geo 
             } else {
 #pragma unroll
                 for (int r = 0; r < 5; ++r) {
-                    const float2 v01 = lds_pair(rbase + bo * RAWSZ + r * X2_RP), v23 = lds_pair(rbase + bo * RAWSZ + r * X2_RP + 2);
-                    const float2 v45 = lds_pair(rbase + bo * RAWSZ + r * X2_RP + 4);
+                    const float2 v01 = lds_pair(rbase + r * X2_RP), v23 = lds_pair(rbase + r * X2_RP + 2);
+                    const float2 v45 = lds_pair(rbase + r * X2_RP + 4);
                     const unsigned rm = min(min(__float_as_uint(v01.y), __float_as_uint(v23.x)),
                                    min(__float_as_uint(v23.y), min(__float_as_uint(v45.x), __float_as_uint(v01.x))));
                     m = r ? min(m, rm) : rm;
@@ -246,19 +237,11 @@ __global__ void __launch_bounds__(256, HHSR_X2_OCC) k_merge_x2(BurstArgs a, Geo 
                 //@ cov_blend
                 if (!ISO) {
                     const int ca = cbase + ay.oc[sa] + ax.oc[sb];  // (ay.oc: times X2_CP already)
-                    const float4 c00 = lds_quad(s_cov + bo * COVSZ + ca), c01 = lds_quad(s_cov + bo * COVSZ + ca + 1);
-                    const float4 c10 = lds_quad(s_cov + bo * COVSZ + ca + X2_CP), c11 = lds_quad(s_cov + bo * COVSZ + ca + X2_CP + 1);
-                    const float gx = ax.f[sb], gy = ay.f[sa];
-                    const float w11 = gx * gy, w01 = gx - w11, w10 = gy - w11, w00 = (1.f - gx) - w10;
-                    const float cxx = fmaf(w11, c11.x, fmaf(w10, c10.x, fmaf(w01, c01.x, w00 * c00.x)));
-                    const float cxy = fmaf(w11, c11.y, fmaf(w10, c10.y, fmaf(w01, c01.y, w00 * c00.y)));
-                    const float cyy = fmaf(w11, c11.w, fmaf(w10, c10.w, fmaf(w01, c01.w, w00 * c00.w)));
+                    const float4 c00 = lds_quad(s_cov + ca), c01 = lds_quad(s_cov + ca + 1);
+                    const float4 c10 = lds_quad(s_cov + ca + X2_CP), c11 = lds_quad(s_cov + ca + X2_CP + 1);
+                    HHSR_COV_BLEND(c00, c01, c10, c11, ax.f[sb], ay.f[sa])
                     //@ inverse
-                    const float det = fmaf(cxx, cyy, -(cxy * cxy));
-                    const float s1 = __builtin_amdgcn_rcpf(det) * X2_KEXP;
-                    ixx = s1 * cyy;
-                    ixy = (-2.f * s1) * cxy;
-                    iyy = s1 * cxx;
+                    HHSR_COV_INVERSE()
                     if (isref_s >= 0) {  // wave-uniform, and kept a real branch by the empty asm statement: if-converted, the reference
                         // frame's rule costs a compare and three v_cndmask (half rate) per sub-pixel of EVERY frame
                         asm volatile("; ref identity");
@@ -276,7 +259,7 @@ __global__ void __launch_bounds__(256, HHSR_X2_OCC) k_merge_x2(BurstArgs a, Geo 
                 // copy whose shift makes column tx + e even
                 //@ tap_setup
                 const int mcol = px + ax.e[sb];  // 0, 1, 2
-                const float* __restrict__ rp = ((mcol & 1) ? s_rawB : s_rawA) + bo * RAWSZ + tyrp + (ay.e[sa] * X2_RP + (mcol & 2));  // (scalar part apart)
+                const float* __restrict__ rp = ((mcol & 1) ? s_rawB : s_rawA) + tyrp + (ay.e[sa] * X2_RP + (mcol & 2));  // (scalar part apart)
                 const float dx0 = ax.d0[sb], dy0 = ay.d0[sa];
                 const float dxs[3] = {dx0 - 1.f, dx0, dx0 + 1.f};
                 float sv[2][2], sd[2][2];  // by parity of the tap offset (di + 1, dj + 1)
@@ -325,38 +308,24 @@ __global__ void __launch_bounds__(256, HHSR_X2_OCC) k_merge_x2(BurstArgs a, Geo 
                 // tap parity (a, b) is colour class (a ^ by, b ^ bx): red sits at parity (ri ^ by, rj ^ bx), blue diagonally
                 // opposite, the greens on the other diagonal — four wave-uniform arrangements
                 const int ra = ri ^ by, rb = rj ^ bx;
-#define HHSR_FOLD3(RA, RB)                                                                    \
-    {                                                                                         \
-        nacc[sa][sb][0] = fmaf(local_r, sv[RA][RB], nacc[sa][sb][0]);                         \
-        dacc[sa][sb][0] = fmaf(local_r, sd[RA][RB], dacc[sa][sb][0]);                         \
-        nacc[sa][sb][1] = fmaf(local_r, sv[RA ^ 1][RB] + sv[RA][RB ^ 1], nacc[sa][sb][1]);    \
-        dacc[sa][sb][1] = fmaf(local_r, sd[RA ^ 1][RB] + sd[RA][RB ^ 1], dacc[sa][sb][1]);    \
-        nacc[sa][sb][2] = fmaf(local_r, sv[RA ^ 1][RB ^ 1], nacc[sa][sb][2]);                 \
-        dacc[sa][sb][2] = fmaf(local_r, sd[RA ^ 1][RB ^ 1], dacc[sa][sb][2]);                 \
-    }
                 if (ra) {
-                    if (rb) { asm volatile("; fold 11"); HHSR_FOLD3(1, 1) asm volatile("; end 11"); }
-                    else { asm volatile("; fold 10"); HHSR_FOLD3(1, 0) asm volatile("; end 10"); }
+                    if (rb) { asm volatile("; fold 11"); HHSR_FOLD3(local_r, 1, 1) asm volatile("; end 11"); }
+                    else { asm volatile("; fold 10"); HHSR_FOLD3(local_r, 1, 0) asm volatile("; end 10"); }
                 } else {
-                    if (rb) { asm volatile("; fold 01"); HHSR_FOLD3(0, 1) asm volatile("; end 01"); }
-                    else { asm volatile("; fold 00"); HHSR_FOLD3(0, 0) asm volatile("; end 00"); }
+                    if (rb) { asm volatile("; fold 01"); HHSR_FOLD3(local_r, 0, 1) asm volatile("; end 01"); }
+                    else { asm volatile("; fold 00"); HHSR_FOLD3(local_r, 0, 0) asm volatile("; end 00"); }
                 }
-#undef HHSR_FOLD3
             }
     };
     //@ loop
-    auto frame_n = [&](int n, const float2 fl, float lr, int bo) {
-        frame(std::false_type{}, n >= a.n, fl, lr, bo, n);
-    };
     if (nloop > nfirst) prefetch(nfirst);
     for (int n = nfirst; n < nloop; ++n) {
         __syncthreads();  // the previous frame's taps are done with the LDS windows
-        stage(n, 0);
-        const float2 fl = sfl;
+        stage(n);
         const float lr = sr;
         __syncthreads();
         if (n + 1 < nloop) prefetch(n + 1);  // in flight while this frame's taps are evaluated
-        frame_n(n, fl, lr, 0);
+        frame(n, lr);
     }
     //@ outside
     if (chain_store) {  // park the accumulators for the final link
@@ -372,24 +341,7 @@ __global__ void __launch_bounds__(256, HHSR_X2_OCC) k_merge_x2(BurstArgs a, Geo 
     // ---- epilogue: CFA classes -> RGB, normalise, store -----------------------------------------------------------------
     const int ly = ly0 + ty, lx = lx0 + tx;
     if (a.flags & HHSR_MERGE_LOAD_ACC) {
-        // chained launches (bursts longer than one launch, multi-GPU finish): per-pixel read-modify-write; the border
-        // bands keep their input for k_merge_border
-#pragma unroll
-        for (int sa = 0; sa < 2; ++sa)
-#pragma unroll
-            for (int sb = 0; sb < 2; ++sb) {
-                const int hi = 2 * ly + sa, hj = 2 * lx + sb;
-                if (border_pixel(g, hi, hj)) continue;
-                const size_t o = ((size_t)(hi - g.row0) * g.sW + hj) * 3;
-                float n3[3], d3[3];
-                xs_rgb<NC>(cfa, nacc[sa][sb], dacc[sa][sb], n3, d3);
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const float nk = num[o + k] + n3[k], dk = den[o + k] + d3[k];
-                    num[o + k] = (a.flags & HHSR_MERGE_DIVIDE) ? nk / dk : nk;
-                    if (a.flags & HHSR_MERGE_STORE_DEN) den[o + k] = dk;
-                }
-            }
+        HHSR_ADD_TO_OUTPUT(2)
         return;
     }
     // whole tile through LDS: rows of 96 floats leave as float4 (k_merge_border overwrites the border bands afterwards)
@@ -424,15 +376,9 @@ __global__ void __launch_bounds__(256, HHSR_X2_OCC) k_merge_x2(BurstArgs a, Geo 
     }
 }
 
-
 void hhsr_launch_merge_x2(bool iso, bool lmin, dim3 grid, hipStream_t s, const BurstArgs& a, const Geo& g, const Cfa4& c,
                           float* num, float* den) {
-    const dim3 block(256);
-    if (lmin) {
-        if (iso) hipLaunchKernelGGL((k_merge_x2<true, true>), grid, block, 0, s, a, g, c, num, den);
-        else hipLaunchKernelGGL((k_merge_x2<false, true>), grid, block, 0, s, a, g, c, num, den);
-    } else {
-        if (iso) hipLaunchKernelGGL((k_merge_x2<true, false>), grid, block, 0, s, a, g, c, num, den);
-        else hipLaunchKernelGGL((k_merge_x2<false, false>), grid, block, 0, s, a, g, c, num, den);
-    }
+    with_bool_tags([&](auto LMIN, auto ISO) {
+        hipLaunchKernelGGL((k_merge_x2<ISO.value, LMIN.value>), grid, dim3(256), 0, s, a, g, c, num, den);
+    }, lmin, iso);
 }

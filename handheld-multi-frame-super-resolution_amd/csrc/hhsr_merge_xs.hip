@@ -79,10 +79,13 @@ __device__ __forceinline__ XsAxis<S> xs_ref_axis(int l, int l0, int off_lr, doub
     return u;
 }
 
+#ifndef HHSR_XS_OCC
+#define HHSR_XS_OCC 2  // k_merge_xs<3>: 54 accumulators per thread; 3 waves per SIMD (168 VGPRs) spills 50 dwords
+#endif
 template <int S, bool ISO, bool LMIN>
 __global__ void __launch_bounds__(256, HHSR_XS_OCC) k_merge_xs(BurstArgs a, Geo g, Cfa4 cfa, float* __restrict__ num,
                                                       float* __restrict__ den) {
-    constexpr int RAWSZ = 20 * X2_RP, COVSZ = CWIN * X2_CP, OP = 3 * S * QT + 4, OROWS = S * QT;
+    constexpr int RAWSZ = QRWIN * X2_RP, COVSZ = CWIN * X2_CP, OP = 3 * S * QT + 4, OROWS = S * QT;
     __shared__ __align__(16) float s_rawA[RAWSZ];
     __shared__ __align__(16) float s_rawB[RAWSZ];
     __shared__ float4 s_cov[COVSZ];
@@ -119,7 +122,7 @@ __global__ void __launch_bounds__(256, HHSR_XS_OCC) k_merge_xs(BurstArgs a, Geo 
         ok = fabsf(fl.x) < 1.0e6f && fabsf(fl.y) < 1.0e6f;  // (NaN fails)
         if (ok) {
             const int ox = xs_comp_org<S>(fl.x, lx0), oy = xs_comp_org<S>(fl.y, ly0);
-            edge_f = !(ox >= 0 && ox + X2_WIN <= g.W && oy >= 0 && oy + X2_WIN <= g.H);
+            edge_f = !(ox >= 0 && ox + QWIN <= g.W && oy >= 0 && oy + QWIN <= g.H);
             // the frame loop's staging takes the origin from here (lane = frame; identical in the four waves) instead of
             // re-deriving it per thread and frame behind a dependent load of the flow vector (k_merge_x2, round 6)
             if (wave == 0) s_frm[lane] = make_float4(__int_as_float(ox), __int_as_float(oy), fl.x, fl.y);
@@ -159,17 +162,7 @@ __global__ void __launch_bounds__(256, HHSR_XS_OCC) k_merge_xs(BurstArgs a, Geo 
     const int rcl = cfa.c[0] == 0 ? 0 : cfa.c[1] == 0 ? 1 : cfa.c[2] == 0 ? 2 : 3;
     const int ri = rcl >> 1, rj = rcl & 1;
 
-    constexpr int rwin = X2_WIN, cwin = QT / 2 + 3;
-    const int e0 = tid, e1 = tid + 256;
-    const int e0y = e0 / rwin, e0x = e0 - e0y * rwin, e1y = e1 / rwin, e1x = e1 - e1y * rwin;
-    const int cey = tid / cwin, cex = tid - cey * cwin;
-    const bool has1 = e1 < rwin * rwin, hasc = tid < cwin * cwin;
-    constexpr int RW = QT + 4;
-    const int m0y = tid / RW, m0x = tid - m0y * RW;
-    const int m1 = tid + 256, m1y = m1 / RW, m1x = m1 - m1y * RW;
-    const bool hasm1 = LMIN && m1 < RW * RW;
-    const int moff0 = clampi(ly0 - 2 + m0y, 0, g.H - 1) * g.W + clampi(lx0 - 2 + m0x, 0, g.W - 1);
-    const int moff1 = clampi(ly0 - 2 + m1y, 0, g.H - 1) * g.W + clampi(lx0 - 2 + m1x, 0, g.W - 1);
+    HHSR_STAGE_SLOTS(tid, QCELLS, LMIN)
     const int nloop = a.n + ((a.flags & HHSR_MERGE_DO_REF) ? 1 : 0);
     float pr0 = 0.f, pr1 = 0.f, plr = 0.f, plr1 = 0.f;
     float4 pc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -330,16 +323,8 @@ __global__ void __launch_bounds__(256, HHSR_XS_OCC) k_merge_xs(BurstArgs a, Geo 
                 }
             }
             if (!ISO) {
-                const float gx = gx_e, gy = gy_e;
-                const float w11 = gx * gy, w01 = gx - w11, w10 = gy - w11, w00 = (1.f - gx) - w10;
-                const float cxx = fmaf(w11, cur.c11.x, fmaf(w10, cur.c10.x, fmaf(w01, cur.c01.x, w00 * cur.c00.x)));
-                const float cxy = fmaf(w11, cur.c11.y, fmaf(w10, cur.c10.y, fmaf(w01, cur.c01.y, w00 * cur.c00.y)));
-                const float cyy = fmaf(w11, cur.c11.w, fmaf(w10, cur.c10.w, fmaf(w01, cur.c01.w, w00 * cur.c00.w)));
-                const float det = fmaf(cxx, cyy, -(cxy * cxy));
-                const float s1 = __builtin_amdgcn_rcpf(det) * X2_KEXP;
-                ixx = s1 * cyy;
-                ixy = (-2.f * s1) * cxy;
-                iyy = s1 * cxx;
+                HHSR_COV_BLEND(cur.c00, cur.c01, cur.c10, cur.c11, gx_e, gy_e)
+                HHSR_COV_INVERSE()
                 if (isref_s) {  // wave-uniform; a real branch (see k_merge_x2)
                     asm volatile("; ref identity");
                     if (!(fabsf(det) > 1e-10f)) {
@@ -348,7 +333,7 @@ __global__ void __launch_bounds__(256, HHSR_XS_OCC) k_merge_xs(BurstArgs a, Geo 
                         iyy = X2_KEXP;
                     }
                 }
-                const float probe = fmaf(0.f, ixx, fmaf(0.f, ixy, 0.f * iyy));
+                const float probe = fmaf(0.f, ixx, fmaf(0.f, ixy, 0.f * iyy));  // (one NaN test for the three, as in k_merge_x2)
                 finite = probe == probe;
             }
             const float dx0 = ax.d0[sb], dy0 = ay.d0[sa];
@@ -392,23 +377,13 @@ __global__ void __launch_bounds__(256, HHSR_XS_OCC) k_merge_xs(BurstArgs a, Geo 
             // tap parity (a, b) is colour class (a ^ by, b ^ bx): red sits at parity (ri ^ by, rj ^ bx), blue diagonally
             // opposite, the greens on the other diagonal — four wave-uniform arrangements
             const int ra = ri ^ by, rb = rj ^ bx;
-#define HHSR_FOLD3(RA, RB)                                                                    \
-    {                                                                                         \
-        nacc[sa][sb][0] = fmaf(r_eff, sv[RA][RB], nacc[sa][sb][0]);                           \
-        dacc[sa][sb][0] = fmaf(r_eff, sd[RA][RB], dacc[sa][sb][0]);                           \
-        nacc[sa][sb][1] = fmaf(r_eff, sv[RA ^ 1][RB] + sv[RA][RB ^ 1], nacc[sa][sb][1]);      \
-        dacc[sa][sb][1] = fmaf(r_eff, sd[RA ^ 1][RB] + sd[RA][RB ^ 1], dacc[sa][sb][1]);      \
-        nacc[sa][sb][2] = fmaf(r_eff, sv[RA ^ 1][RB ^ 1], nacc[sa][sb][2]);                   \
-        dacc[sa][sb][2] = fmaf(r_eff, sd[RA ^ 1][RB ^ 1], dacc[sa][sb][2]);                   \
-    }
             if (ra) {
-                if (rb) { asm volatile("; xs fold 11"); HHSR_FOLD3(1, 1) asm volatile("; xs end 11"); }
-                else { asm volatile("; xs fold 10"); HHSR_FOLD3(1, 0) asm volatile("; xs end 10"); }
+                if (rb) { asm volatile("; xs fold 11"); HHSR_FOLD3(r_eff, 1, 1) asm volatile("; xs end 11"); }
+                else { asm volatile("; xs fold 10"); HHSR_FOLD3(r_eff, 1, 0) asm volatile("; xs end 10"); }
             } else {
-                if (rb) { asm volatile("; xs fold 01"); HHSR_FOLD3(0, 1) asm volatile("; xs end 01"); }
-                else { asm volatile("; xs fold 00"); HHSR_FOLD3(0, 0) asm volatile("; xs end 00"); }
+                if (rb) { asm volatile("; xs fold 01"); HHSR_FOLD3(r_eff, 0, 1) asm volatile("; xs end 01"); }
+                else { asm volatile("; xs fold 00"); HHSR_FOLD3(r_eff, 0, 0) asm volatile("; xs end 00"); }
             }
-#undef HHSR_FOLD3
             cur = nxt;
         }
     }
@@ -417,22 +392,7 @@ __global__ void __launch_bounds__(256, HHSR_XS_OCC) k_merge_xs(BurstArgs a, Geo 
     else run_frames(std::false_type{});
     if (a.acc_r) a.acc_r[ridx] = ((a.flags & HHSR_MERGE_LOAD_ACC) ? a.acc_r[ridx] : 0.f) + racc;
     if (a.flags & HHSR_MERGE_LOAD_ACC) {
-#pragma unroll
-        for (int sa = 0; sa < S; ++sa)
-#pragma unroll
-            for (int sb = 0; sb < S; ++sb) {
-                const int hi = S * ly + sa, hj = S * lx + sb;
-                if (border_pixel(g, hi, hj)) continue;
-                const size_t o = ((size_t)(hi - g.row0) * g.sW + hj) * 3;
-                float n3[3], d3[3];
-                xs_rgb<NC>(cfa, nacc[sa][sb], dacc[sa][sb], n3, d3);
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const float nk = num[o + k] + n3[k], dk = den[o + k] + d3[k];
-                    num[o + k] = (a.flags & HHSR_MERGE_DIVIDE) ? nk / dk : nk;
-                    if (a.flags & HHSR_MERGE_STORE_DEN) den[o + k] = dk;
-                }
-            }
+        HHSR_ADD_TO_OUTPUT(S)
         return;
     }
     const int npass = (a.flags & HHSR_MERGE_STORE_DEN) ? 2 : 1;
@@ -461,15 +421,9 @@ __global__ void __launch_bounds__(256, HHSR_XS_OCC) k_merge_xs(BurstArgs a, Geo 
     }
 }
 
-
 void hhsr_launch_merge_x3(bool iso, bool lmin, dim3 grid, hipStream_t s, const BurstArgs& a, const Geo& g, const Cfa4& c,
                           float* num, float* den) {
-    const dim3 block(256);
-    if (lmin) {
-        if (iso) hipLaunchKernelGGL((k_merge_xs<3, true, true>), grid, block, 0, s, a, g, c, num, den);
-        else hipLaunchKernelGGL((k_merge_xs<3, false, true>), grid, block, 0, s, a, g, c, num, den);
-    } else {
-        if (iso) hipLaunchKernelGGL((k_merge_xs<3, true, false>), grid, block, 0, s, a, g, c, num, den);
-        else hipLaunchKernelGGL((k_merge_xs<3, false, false>), grid, block, 0, s, a, g, c, num, den);
-    }
+    with_bool_tags([&](auto LMIN, auto ISO) {
+        hipLaunchKernelGGL((k_merge_xs<3, ISO.value, LMIN.value>), grid, dim3(256), 0, s, a, g, c, num, den);
+    }, lmin, iso);
 }
