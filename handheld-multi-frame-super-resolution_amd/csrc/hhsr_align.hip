@@ -560,7 +560,8 @@ extern "C" int hhsr_ica(const float* ref, const float* gx, const float* gy, int 
 //     zero outside the LEVEL, exactly the values hhsr_grad_hessian writes), and
 //   * ONE moving window of (TS + 2r + 2M + 1)^2 pixels around round(flow_in) that serves both the
 //     (2r+1)^2 block-matching candidates and the bilinear taps of the ICA iterations,
-// i.e. ~3.3 vector loads per pixel for the whole level step (separate kernels: ~7).  The window is staged
+// i.e. ~3.3 vector loads per pixel for the whole level step (separate kernels: ~7); where the wave walks the frames of
+// the launch (r < 4, large grids: see k_align_wave) the reference tile's 1.3 are paid once per chunk.  The window is staged
 // with the block-matching border rule (L2: clamp-to-edge, L1: zero-fill); ICA's own rule (zero outside /
 // clamped coordinates for TS = 8) differs only where the window leaves the moving level, and there
 // (wave-uniform test) the ICA taps are read from global memory with the exact rule.
@@ -571,7 +572,9 @@ extern "C" int hhsr_ica(const float* ref, const float* gx, const float* gy, int 
 //     divisions, and for tiles whose windows lie inside their level (wave-uniform test) no per-element bounds
 //     logic either — one 64-bit add per load, LDS stores at immediate offsets;
 //   * the waves of a workgroup never share LDS data: a wave-level fence replaces __syncthreads();
-//   * the (2r+1)^2 <= 9 candidate loop is unrolled (immediate LDS offsets).
+//   * the (2r+1)^2 <= 9 candidate loop is unrolled (immediate LDS offsets);
+//   * level 0 stages the reference tile, loads the Hessian and derives the geometry once per tile and chunk of frames, not
+//     once per frame: 562 instead of 628 VALU instructions per tile and frame (profiles/align_chunk_loop.txt).
 // a <- [a.lo + a.hi | b.lo + b.hi] over the two 32-lane halves (v_permlane32_swap: vdst[32..63] <-> src[0..31])
 __device__ __forceinline__ float swap32_add(float a, float b) {
     const auto t = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
@@ -593,23 +596,30 @@ struct Stage2D {  // N x N window, lane -> (row lane / CW + k * (64 / CW), colum
     static constexpr int RPP = HHSR_WAVE / CW, NK = (N + RPP - 1) / RPP;
 };
 
-struct AlignFrames {  // blockIdx.y = frame of the batch (the frames share the reference level)
+#ifndef HHSR_ALIGN_LOOP_MIN_TILES
+#define HHSR_ALIGN_LOOP_MIN_TILES 24576  // launches of fewer tiles keep one wave per (tile, frame): hhsr_align_level_batch (A/B)
+#endif
+struct AlignFrames {  // the frames of one launch (they share the reference level)
     const float* mov[HHSR_MAX_BATCH];
     float* flow[HHSR_MAX_BATCH];
     const float2* coarse[HHSR_MAX_BATCH];  // all NULL or all set
 };
 
+// One wave per tile; the wave walks the frames [blockIdx.y * fpw, min(nf, (blockIdx.y + 1) * fpw)) of the launch (fpw = nf:
+// all of them, grid.y = 1; fpw = 1: one wave per (tile, frame)).  Everything that depends on the reference tile alone is
+// done once, before the frame loop: tile coordinates and the lane's row / column mapping, the reference tile + halo staged
+// to LDS, the tile's Hessian with det and 1 / det, the source tile of the coarser flow, the lane halves of the staging
+// offsets and (KEEP) the lane's reference values and gradients, which then stay in registers.  Per frame: the incoming
+// flow, the moving window, block matching, the ICA iterations and the store of the flow — the expressions, operands and
+// association of the one-frame kernel, so a frame's flow does not depend on the frames launched with it.
 template <int TS, int R, bool L1>
 __global__ void __launch_bounds__(256) k_align_wave(const float* __restrict__ ref, int rh, int rw, int ref_pitch,
-                                                     const float* __restrict__ hess, AlignFrames fr,
+                                                     const float* __restrict__ hess, AlignFrames fr, int nf, int fpw,
                                                      int mh, int mw, int mov_pitch, int nx,
                                                      int ntiles, int mode, int n_iter,
                                                      int cny, int cnx, int rep,
                                                      float mult) {
     constexpr int r = R;
-    const float* __restrict__ mov = fr.mov[blockIdx.y];
-    float* __restrict__ flow = fr.flow[blockIdx.y];
-    const float2* __restrict__ coarse = fr.coarse[blockIdx.y];
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int M = ICA_M;
     constexpr int RS = TS + 2, RP = RS | 1;            // reference tile + halo
@@ -623,41 +633,33 @@ __global__ void __launch_bounds__(256) k_align_wave(const float* __restrict__ re
     constexpr bool PERM = HHSR_ALIGN_PERM && TS == 16 && R == 1;
     constexpr int WS = TS + 2 * r + 2 * M + 1, WP = PERM ? ((WS + 7) & ~15) + 8 : (WS | 1);
     constexpr int slice = (RS * RP + WS * WP + 3) & ~3;
+    // the lane's reference values and gradients live in registers across the frames where that costs no resident wave
+    // (3 PPT VGPRs: r = 1, and <8, 2> with one pixel per lane); the others re-read them per frame from the tile staged
+    // once.  r = 4 has no frame loop (LOOP false: the launcher gives it fpw = 1): its 81 partial costs put <16, 4, false>
+    // on an occupancy step (96 VGPRs, 5 waves per SIMD), and what a loop keeps live — even with every lane address
+    // re-derived per frame — takes a resident wave from it (104 VGPRs; profiles/align_chunk_loop.txt)
+    constexpr bool LOOP = R != 4, KEEP = LOOP && (R == 1 || TS == 8);
     float* s_ref = lds + (size_t)wave * slice;
     float* s_win = s_ref + RS * RP;
     const int tile = xcd_remap(blockIdx.x, gridDim.x) * 4 + wave;  // neighbouring tiles share window halos: same L2
     if (tile >= ntiles) return;  // wave-uniform; no workgroup barrier below
     const int ty = tile / nx, tx = tile - ty * nx;
-    float* fl = flow + (size_t)tile * 2;
-    // incoming flow: this level's array, or (fused nearest-neighbour upscaling, alignment.py:150-172) the coarser
-    // level's flow of tile (ty/rep, tx/rep) times the level factor — zero past the coarse grid — or zero (rep < 0)
-    float fin0 = 0.f, fin1 = 0.f;
-    if (coarse) {
+    // source tile (ty/rep, tx/rep) of the coarser level's flow; -1: past the coarse grid (or no coarse flows)
+    int csrc = -1;
+    if (fr.coarse[0]) {
         const int sy = ty / rep, sx = tx / rep;
-        if (sy < cny && sx < cnx) {
-            const float2 c = coarse[(size_t)sy * cnx + sx];
-            fin0 = c.x * mult;
-            fin1 = c.y * mult;
-        }
-    } else if (rep >= 0) {
-        fin0 = fl[0];
-        fin1 = fl[1];
+        if (sy < cny && sx < cnx) csrc = sy * cnx + sx;
     }
-    const float f0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, fin0)));
-    const float f1 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, fin1)));
-    const float r0 = rintf(f0), r1 = rintf(f1);  // round-half-even
-    const int ox = tx * TS + (int)r0 - r - M, oy = ty * TS + (int)r1 - r - M;  // window origin in the moving level
+    // windows are staged through a 2-D lane mapping; all global loads of a window are issued back to back into
+    // registers, then stored to LDS (a load -> store loop serialises on memory latency: 14-40 round trips per tile)
+    constexpr int CWR = RS <= 32 ? 32 : 64, CWW = WS <= 32 ? 32 : 64;
+    using SR = Stage2D<RS, CWR>;
+    using SW = Stage2D<WS, CWW>;
     {
-        // all global loads of the two windows are issued back to back into registers, then stored to LDS
-        // (a load -> store loop serialises on memory latency: 14-40 round trips per tile)
-        constexpr int CWR = RS <= 32 ? 32 : 64, CWW = WS <= 32 ? 32 : 64;
-        using SR = Stage2D<RS, CWR>;
-        using SW = Stage2D<WS, CWW>;
-        float vr[SR::NK], vw[SW::NK];
-        const int jr = lane % CWR, ir = lane / CWR, jw = lane % CWW, iw = lane / CWW;
+        float vr[SR::NK];
+        const int jr = lane % CWR, ir = lane / CWR;
         const int rx0 = tx * TS - 1, ry0 = ty * TS - 1;
         const bool ref_in = rx0 >= 0 && ry0 >= 0 && rx0 + RS <= rw && ry0 + RS <= rh;
-        const bool win_in = ox >= 0 && oy >= 0 && ox + WS <= mw && oy + WS <= mh;
         // (window origins are wave-uniform: the row base advances in SGPRs, every load of a window shares ONE 32-bit lane
         // offset — `global_load ... v_off, s[base:base+1]` — instead of a 64-bit address per load; round 6)
         if (ref_in) {  // columns past the window re-read its last column (never stored)
@@ -677,197 +679,253 @@ __global__ void __launch_bounds__(256) k_align_wave(const float* __restrict__ re
                             ? ref[(size_t)y * ref_pitch + x] : 0.f;
             }
         }
-        if (win_in) {
-            const char* qb = reinterpret_cast<const char*>(mov + (size_t)oy * mov_pitch + ox);
-            const unsigned voff = (unsigned)(iw * mov_pitch + min(jw, WS - 1)) * 4u;
-#pragma unroll
-            for (int k = 0; k < SW::NK; ++k) {
-                const bool tail = (k + 1) * SW::RPP > WS;
-                vw[k] = (!tail || iw + k * SW::RPP < WS)
-                            ? *reinterpret_cast<const float*>(qb + (size_t)k * SW::RPP * mov_pitch * 4 + voff) : 0.f;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < SW::NK; ++k) {
-                const int y = oy + iw + k * SW::RPP, x = ox + jw;
-                const bool inw = jw < WS && iw + k * SW::RPP < WS;
-                if (L1) vw[k] = (inw && y >= 0 && y < mh && x >= 0 && x < mw) ? mov[(size_t)y * mov_pitch + x] : 0.f;
-                else vw[k] = inw ? mov[(size_t)clampi(y, 0, mh - 1) * mov_pitch + clampi(x, 0, mw - 1)] : 0.f;
-            }
-        }
         if (jr < RS) {
             float* d = s_ref + ir * RP + jr;
 #pragma unroll
             for (int k = 0; k < SR::NK; ++k)
                 if ((k + 1) * SR::RPP <= RS || ir + k * SR::RPP < RS) d[k * SR::RPP * RP] = vr[k];
         }
-        if (jw < WS) {
-            float* d = s_win + iw * WP + jw;
-#pragma unroll
-            for (int k = 0; k < SW::NK; ++k)
-                if ((k + 1) * SW::RPP <= WS || iw + k * SW::RPP < WS) d[k * SW::RPP * WP] = vw[k];
-        }
     }
     // LDS operations of one wave complete in order; the slice is private to the wave
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (KEEP) {  // (the others first read the tile behind the fence of the first window)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
     // lane's pixels p = lane + 64k: row lane / TS + k * (64 / TS), column lane % TS
     constexpr int RSTEP = HHSR_WAVE / TS > 0 ? HHSR_WAVE / TS : 1;
-    // (PERM: the four 16-lane groups own rows 0, 2, 1, 3 (+ 4k) of the tile)
-    const int li = PERM ? (((lane >> 4) & 1) << 1) | (lane >> 5) : lane / TS, lj = lane % TS;
-    // ---------------- block matching ----------------
-    float nfx = f0, nfy = f1;  // flow after block matching
-    if (L1 && mode == 1) {     // "L1_ref_effective": flow <- round(flow)
-        nfx = r0;
-        nfy = r1;
-    } else {
-        CostIdx best{INFINITY, 0};
-        if (n <= 16 && TS * TS >= HHSR_WAVE) {
-            float rv[PPT];
-            const float* rb = s_ref + (li + 1) * RP + lj + 1;
-            const float* wb = s_win + (li + M) * WP + lj + M;
-#pragma unroll
-            for (int k = 0; k < PPT; ++k) rv[k] = rb[k * RSTEP * RP];
-#pragma unroll
-            for (int c = 0; c < n; ++c) {
-                const int dy = c / n1, dx = c - dy * n1;
-                float acc = 0.f;
-#pragma unroll
-                for (int k = 0; k < PPT; ++k) {
-                    const float d = rv[k] - wb[(k * RSTEP + dy) * WP + dx];
-                    acc += L1 ? fabsf(d) : d * d;
-                }
-                acc = wave_sum_uniform(acc);
-                if (acc < best.c) {
-                    best.c = acc;
-                    best.i = c;
-                }
-            }
-        } else {
-            // (2r+1)^2 = 25 or 81 candidates.  A lane owns PPT vertically adjacent pixels of one column, so a
-            // window value serves up to PPT (pixel, dy) pairs from a register: (PPT + 2r)(2r + 1) LDS reads per
-            // lane instead of 2 per difference, every candidate's partial cost in its own VGPR.
-            constexpr int NQ = (n + 3) / 4;
-            float acc[4 * NQ];
-#pragma unroll
-            for (int c = 0; c < 4 * NQ; ++c) acc[c] = 0.f;
-            const int lc = lane % TS, lr = (lane / TS) * PPT;
-            float rv[PPT];
-            const float* rb = s_ref + (lr + 1) * RP + lc + 1;
-            const float* wb = s_win + (lr + M) * WP + lc + M;
-#pragma unroll
-            for (int k = 0; k < PPT; ++k) rv[k] = rb[k * RP];
-#pragma unroll
-            for (int rr = 0; rr < PPT + 2 * r; ++rr) {
-#pragma unroll
-                for (int dx = 0; dx < n1; ++dx) {
-                    const float w = wb[rr * WP + dx];
-#pragma unroll
-                    for (int k = 0; k < PPT; ++k) {
-                        const int dy = rr - k;
-                        if (dy >= 0 && dy < n1) {
-                            const float d = rv[k] - w;
-                            acc[dy * n1 + dx] = L1 ? acc[dy * n1 + dx] + fabsf(d) : fmaf(d, d, acc[dy * n1 + dx]);
-                        }
-                    }
-                }
-            }
-            // 4 candidates per step: the lane-half and row swaps of gfx950 fold the 64 partials of candidates
-            // (4q, 4q+1, 4q+2, 4q+3) into the 16-lane rows (0, 2, 1, 3) of ONE register, a 4-step DPP row
-            // reduction finishes all four at once (10 instructions per 4 candidates, fixed association).
-            const int roff = ((lane >> 4) & 1) * 2 + (lane >> 5);  // rows 0..3 hold candidates 4q + {0, 2, 1, 3}
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                const float s01 = swap32_add(acc[4 * q], acc[4 * q + 1]);      // [c0 | c1]
-                const float s23 = swap32_add(acc[4 * q + 2], acc[4 * q + 3]);  // [c2 | c3]
-                float v = swap16_add(s01, s23);                                // rows [c0, c2, c1, c3]
-                v += HHSR_DPP(v, 0xB1, 0xf);
-                v += HHSR_DPP(v, 0x4E, 0xf);
-                v += HHSR_DPP(v, 0x141, 0xf);
-                v += HHSR_DPP(v, 0x140, 0xf);
-                const int idx = 4 * q + roff;
-                const float cost = idx < n ? v : INFINITY;
-                if (cost < best.c) {  // idx grows with q: strict < keeps the first minimum of this row
-                    best.c = cost;
-                    best.i = idx;
-                }
-            }
-            best = wave_argmin(best);
-        }
-        const int dy = best.i / n1 - r, dx = best.i % n1 - r;
-        if (L1) {  // flow <- round(flow) + shift
-            nfx = r0 + (float)dx;
-            nfy = r1 + (float)dy;
-        } else {   // shift added to the UN-rounded flow
-            nfx = f0 + (float)dx;
-            nfy = f1 + (float)dy;
-        }
-    }
-    // ---------------- ICA ----------------
     const float* h = hess + (size_t)tile * 4;
     const float A00 = h[0], A01 = h[1], A10 = h[2], A11 = h[3];
     const float det = A00 * A11 - A01 * A10;
-    float fxv = nfx, fyv = nfy;
-    if (!(fabsf(det) < 1e-10f)) {  // else: not solvable, the block-matching result stands (ICA.py:124-125)
-        const float det_inv = 1.0f / det;
-        float rc[PPT], lgx[PPT], lgy[PPT];
+    const bool solvable = !(fabsf(det) < 1e-10f);  // else the block-matching result stands (ICA.py:124-125)
+    const float det_inv = 1.0f / det;
+    float rck[PPT], gxk[PPT], gyk[PPT];  // KEEP: pixel (li + k RSTEP, lj), the lane's k-th pixel
+    if (KEEP) {
+        const int li = PERM ? (((lane >> 4) & 1) << 1) | (lane >> 5) : lane / TS, lj = lane % TS;
 #pragma unroll
         for (int k = 0; k < PPT; ++k) {
-            const float* c = s_ref + (li + k * RSTEP + 1) * RP + lj + 1;  // pixel (li + k RSTEP, lj): the lane's k-th pixel
-            rc[k] = c[0];
-            lgx[k] = c[1] - c[-1];
-            lgy[k] = c[RP] - c[-RP];
-        }
-        for (int it = 0; it < n_iter; ++it) {
-            const float tx_ = truncf(fxv), ty_ = truncf(fyv);
-            const float frx = fxv - tx_, fry = fyv - ty_;  // signed fraction of modf (D11)
-            const int ix = (int)tx_, iy = (int)ty_;
-            // LDS coordinates of the tile's first tap; usable when all taps are inside the staged window AND
-            // the tapped region lies inside the moving level (where every border rule agrees)
-            const int sx = tx * TS + ix - ox, sy = ty * TS + iy - oy;
-            const bool in_lds = sx >= 0 && sy >= 0 && sx + TS + 1 <= WS && sy + TS + 1 <= WS &&
-                                tx * TS + ix >= 0 && ty * TS + iy >= 0 && tx * TS + ix + TS < mw &&
-                                ty * TS + iy + TS < mh;
-            float B0 = 0.f, B1 = 0.f;
-            const float* wl = s_win + (li + sy) * WP + (lj + sx);
-#pragma unroll
-            for (int k = 0; k < PPT; ++k) {
-                const int i = li + k * RSTEP, j = lj;
-                float m00, m01, m10, m11;
-                if (in_lds) {
-                    const float* w = TS * TS >= HHSR_WAVE ? wl + k * RSTEP * WP : s_win + (i + sy) * WP + (j + sx);
-                    m00 = w[0];
-                    m01 = w[1];
-                    m10 = w[WP];
-                    m11 = w[WP + 1];
-                } else if (TS == 8) {  // clamped coordinates (ICA.py:152-156)
-                    const int x0 = clampi(tx * TS + j + ix, 0, mw - 1), y0 = clampi(ty * TS + i + iy, 0, mh - 1);
-                    const int x1 = clampi(x0 + 1, 0, mw - 1), y1 = clampi(y0 + 1, 0, mh - 1);
-                    m00 = mov[(size_t)y0 * mov_pitch + x0];
-                    m01 = mov[(size_t)y0 * mov_pitch + x1];
-                    m10 = mov[(size_t)y1 * mov_pitch + x0];
-                    m11 = mov[(size_t)y1 * mov_pitch + x1];
-                } else {  // zero outside (ICA.py:240-243)
-                    const int x0 = tx * TS + j + ix, y0 = ty * TS + i + iy;
-                    const bool xa = x0 >= 0 && x0 < mw, xb = x0 + 1 >= 0 && x0 + 1 < mw;
-                    const bool ya = y0 >= 0 && y0 < mh, yb = y0 + 1 >= 0 && y0 + 1 < mh;
-                    m00 = (ya && xa) ? mov[(size_t)y0 * mov_pitch + x0] : 0.f;
-                    m01 = (ya && xb) ? mov[(size_t)y0 * mov_pitch + x0 + 1] : 0.f;
-                    m10 = (yb && xa) ? mov[(size_t)(y0 + 1) * mov_pitch + x0] : 0.f;
-                    m11 = (yb && xb) ? mov[(size_t)(y0 + 1) * mov_pitch + x0 + 1] : 0.f;
-                }
-                ica_tap(m00, m01, m10, m11, frx, fry, rc[k], lgx[k], lgy[k], B0, B1);
-            }
-            B0 = wave_allsum(B0);
-            B1 = wave_allsum(B1);
-            fxv = fxv + det_inv * (A11 * B0 - A01 * B1);
-            fyv = fyv + det_inv * (-A10 * B0 + A00 * B1);
+            const float* c = s_ref + (li + k * RSTEP + 1) * RP + lj + 1;
+            rck[k] = c[0];
+            gxk[k] = c[1] - c[-1];
+            gyk[k] = c[RP] - c[-RP];
         }
     }
-    if (lane == 0) {
-        fl[0] = fxv;
-        fl[1] = fyv;
+    const int f_beg = blockIdx.y * fpw, f_end = LOOP ? min(nf, f_beg + fpw) : f_beg + 1;
+    for (int f = f_beg; f < f_end; ++f) {
+        // (what follows from the lane index alone is loop-invariant: the lane halves of the staging offsets, LDS addresses)
+        const int jw = lane % CWW, iw = lane / CWW;
+        const unsigned woff = (unsigned)(iw * mov_pitch + min(jw, WS - 1)) * 4u;  // lane half of the in-level window loads
+        float* const wdst = s_win + iw * WP + jw;
+        // (PERM: the four 16-lane groups own rows 0, 2, 1, 3 (+ 4k) of the tile)
+        const int li = PERM ? (((lane >> 4) & 1) << 1) | (lane >> 5) : lane / TS, lj = lane % TS;
+        const float* __restrict__ mov = fr.mov[f];
+        float* fl = fr.flow[f] + (size_t)tile * 2;
+        const float2* __restrict__ coarse = fr.coarse[f];
+        // incoming flow: this level's array, or (fused nearest-neighbour upscaling, alignment.py:150-172) the coarser
+        // level's flow of tile (ty/rep, tx/rep) times the level factor — zero past the coarse grid — or zero (rep < 0)
+        float fin0 = 0.f, fin1 = 0.f;
+        if (coarse) {
+            if (csrc >= 0) {
+                const float2 c = coarse[csrc];
+                fin0 = c.x * mult;
+                fin1 = c.y * mult;
+            }
+        } else if (rep >= 0) {
+            fin0 = fl[0];
+            fin1 = fl[1];
+        }
+        const float f0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, fin0)));
+        const float f1 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, fin1)));
+        const float r0 = rintf(f0), r1 = rintf(f1);  // round-half-even
+        const int ox = tx * TS + (int)r0 - r - M, oy = ty * TS + (int)r1 - r - M;  // window origin in the moving level
+        {
+            float vw[SW::NK];
+            const bool win_in = ox >= 0 && oy >= 0 && ox + WS <= mw && oy + WS <= mh;
+            if (win_in) {
+                const char* qb = reinterpret_cast<const char*>(mov + (size_t)oy * mov_pitch + ox);
+#pragma unroll
+                for (int k = 0; k < SW::NK; ++k) {
+                    const bool tail = (k + 1) * SW::RPP > WS;
+                    vw[k] = (!tail || iw + k * SW::RPP < WS)
+                                ? *reinterpret_cast<const float*>(qb + (size_t)k * SW::RPP * mov_pitch * 4 + woff) : 0.f;
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < SW::NK; ++k) {
+                    const int y = oy + iw + k * SW::RPP, x = ox + jw;
+                    const bool inw = jw < WS && iw + k * SW::RPP < WS;
+                    if (L1) vw[k] = (inw && y >= 0 && y < mh && x >= 0 && x < mw) ? mov[(size_t)y * mov_pitch + x] : 0.f;
+                    else vw[k] = inw ? mov[(size_t)clampi(y, 0, mh - 1) * mov_pitch + clampi(x, 0, mw - 1)] : 0.f;
+                }
+            }
+            if (jw < WS) {
+#pragma unroll
+                for (int k = 0; k < SW::NK; ++k)
+                    if ((k + 1) * SW::RPP <= WS || iw + k * SW::RPP < WS) wdst[k * SW::RPP * WP] = vw[k];
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        // ---------------- block matching ----------------
+        float nfx = f0, nfy = f1;  // flow after block matching
+        if (L1 && mode == 1) {     // "L1_ref_effective": flow <- round(flow)
+            nfx = r0;
+            nfy = r1;
+        } else {
+            CostIdx best{INFINITY, 0};
+            if (n <= 16 && TS * TS >= HHSR_WAVE) {
+                float rv[PPT];
+                const float* rb = s_ref + (li + 1) * RP + lj + 1;
+                const float* wb = s_win + (li + M) * WP + lj + M;
+#pragma unroll
+                for (int k = 0; k < PPT; ++k) rv[k] = KEEP ? rck[k] : rb[k * RSTEP * RP];
+#pragma unroll
+                for (int c = 0; c < n; ++c) {
+                    const int dy = c / n1, dx = c - dy * n1;
+                    float acc = 0.f;
+#pragma unroll
+                    for (int k = 0; k < PPT; ++k) {
+                        const float d = rv[k] - wb[(k * RSTEP + dy) * WP + dx];
+                        acc += L1 ? fabsf(d) : d * d;
+                    }
+                    acc = wave_sum_uniform(acc);
+                    if (acc < best.c) {
+                        best.c = acc;
+                        best.i = c;
+                    }
+                }
+            } else {
+                // (2r+1)^2 = 25 or 81 candidates.  A lane owns PPT vertically adjacent pixels of one column, so a
+                // window value serves up to PPT (pixel, dy) pairs from a register: (PPT + 2r)(2r + 1) LDS reads per
+                // lane instead of 2 per difference, every candidate's partial cost in its own VGPR.
+                constexpr int NQ = (n + 3) / 4;
+                float acc[4 * NQ];
+#pragma unroll
+                for (int c = 0; c < 4 * NQ; ++c) acc[c] = 0.f;
+                const int lc = lane % TS, lr = (lane / TS) * PPT;
+                float rv[PPT];
+                const float* rb = s_ref + (lr + 1) * RP + lc + 1;
+                const float* wb = s_win + (lr + M) * WP + lc + M;
+#pragma unroll
+                for (int k = 0; k < PPT; ++k) rv[k] = (KEEP && PPT == 1) ? rck[k] : rb[k * RP];  // (one pixel per lane: the same pixel)
+#pragma unroll
+                for (int rr = 0; rr < PPT + 2 * r; ++rr) {
+#pragma unroll
+                    for (int dx = 0; dx < n1; ++dx) {
+                        const float w = wb[rr * WP + dx];
+#pragma unroll
+                        for (int k = 0; k < PPT; ++k) {
+                            const int dy = rr - k;
+                            if (dy >= 0 && dy < n1) {
+                                const float d = rv[k] - w;
+                                acc[dy * n1 + dx] = L1 ? acc[dy * n1 + dx] + fabsf(d) : fmaf(d, d, acc[dy * n1 + dx]);
+                            }
+                        }
+                    }
+                }
+                // 4 candidates per step: the lane-half and row swaps of gfx950 fold the 64 partials of candidates
+                // (4q, 4q+1, 4q+2, 4q+3) into the 16-lane rows (0, 2, 1, 3) of ONE register, a 4-step DPP row
+                // reduction finishes all four at once (10 instructions per 4 candidates, fixed association).
+                const int roff = ((lane >> 4) & 1) * 2 + (lane >> 5);  // rows 0..3 hold candidates 4q + {0, 2, 1, 3}
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) {
+                    const float s01 = swap32_add(acc[4 * q], acc[4 * q + 1]);      // [c0 | c1]
+                    const float s23 = swap32_add(acc[4 * q + 2], acc[4 * q + 3]);  // [c2 | c3]
+                    float v = swap16_add(s01, s23);                                // rows [c0, c2, c1, c3]
+                    v += HHSR_DPP(v, 0xB1, 0xf);
+                    v += HHSR_DPP(v, 0x4E, 0xf);
+                    v += HHSR_DPP(v, 0x141, 0xf);
+                    v += HHSR_DPP(v, 0x140, 0xf);
+                    const int idx = 4 * q + roff;
+                    const float cost = idx < n ? v : INFINITY;
+                    if (cost < best.c) {  // idx grows with q: strict < keeps the first minimum of this row
+                        best.c = cost;
+                        best.i = idx;
+                    }
+                }
+                best = wave_argmin(best);
+            }
+            const int dy = best.i / n1 - r, dx = best.i % n1 - r;
+            if (L1) {  // flow <- round(flow) + shift
+                nfx = r0 + (float)dx;
+                nfy = r1 + (float)dy;
+            } else {   // shift added to the UN-rounded flow
+                nfx = f0 + (float)dx;
+                nfy = f1 + (float)dy;
+            }
+        }
+        // ---------------- ICA ----------------
+        float fxv = nfx, fyv = nfy;
+        if (solvable) {
+            float rc[PPT], lgx[PPT], lgy[PPT];
+#pragma unroll
+            for (int k = 0; k < PPT; ++k) {
+                if (KEEP) {
+                    rc[k] = rck[k];
+                    lgx[k] = gxk[k];
+                    lgy[k] = gyk[k];
+                } else {
+                    const float* c = s_ref + (li + k * RSTEP + 1) * RP + lj + 1;  // pixel (li + k RSTEP, lj): the lane's k-th pixel
+                    rc[k] = c[0];
+                    lgx[k] = c[1] - c[-1];
+                    lgy[k] = c[RP] - c[-RP];
+                }
+            }
+            for (int it = 0; it < n_iter; ++it) {
+                const float tx_ = truncf(fxv), ty_ = truncf(fyv);
+                const float frx = fxv - tx_, fry = fyv - ty_;  // signed fraction of modf (D11)
+                const int ix = (int)tx_, iy = (int)ty_;
+                // LDS coordinates of the tile's first tap; usable when all taps are inside the staged window AND
+                // the tapped region lies inside the moving level (where every border rule agrees)
+                const int sx = tx * TS + ix - ox, sy = ty * TS + iy - oy;
+                const bool in_lds = sx >= 0 && sy >= 0 && sx + TS + 1 <= WS && sy + TS + 1 <= WS &&
+                                    tx * TS + ix >= 0 && ty * TS + iy >= 0 && tx * TS + ix + TS < mw &&
+                                    ty * TS + iy + TS < mh;
+                float B0 = 0.f, B1 = 0.f;
+                const float* wl = s_win + (li + sy) * WP + (lj + sx);
+#pragma unroll
+                for (int k = 0; k < PPT; ++k) {
+                    const int i = li + k * RSTEP, j = lj;
+                    float m00, m01, m10, m11;
+                    if (in_lds) {
+                        const float* w = TS * TS >= HHSR_WAVE ? wl + k * RSTEP * WP : s_win + (i + sy) * WP + (j + sx);
+                        m00 = w[0];
+                        m01 = w[1];
+                        m10 = w[WP];
+                        m11 = w[WP + 1];
+                    } else if (TS == 8) {  // clamped coordinates (ICA.py:152-156)
+                        const int x0 = clampi(tx * TS + j + ix, 0, mw - 1), y0 = clampi(ty * TS + i + iy, 0, mh - 1);
+                        const int x1 = clampi(x0 + 1, 0, mw - 1), y1 = clampi(y0 + 1, 0, mh - 1);
+                        m00 = mov[(size_t)y0 * mov_pitch + x0];
+                        m01 = mov[(size_t)y0 * mov_pitch + x1];
+                        m10 = mov[(size_t)y1 * mov_pitch + x0];
+                        m11 = mov[(size_t)y1 * mov_pitch + x1];
+                    } else {  // zero outside (ICA.py:240-243)
+                        const int x0 = tx * TS + j + ix, y0 = ty * TS + i + iy;
+                        const bool xa = x0 >= 0 && x0 < mw, xb = x0 + 1 >= 0 && x0 + 1 < mw;
+                        const bool ya = y0 >= 0 && y0 < mh, yb = y0 + 1 >= 0 && y0 + 1 < mh;
+                        m00 = (ya && xa) ? mov[(size_t)y0 * mov_pitch + x0] : 0.f;
+                        m01 = (ya && xb) ? mov[(size_t)y0 * mov_pitch + x0 + 1] : 0.f;
+                        m10 = (yb && xa) ? mov[(size_t)(y0 + 1) * mov_pitch + x0] : 0.f;
+                        m11 = (yb && xb) ? mov[(size_t)(y0 + 1) * mov_pitch + x0 + 1] : 0.f;
+                    }
+                    ica_tap(m00, m01, m10, m11, frx, fry, rc[k], lgx[k], lgy[k], B0, B1);
+                }
+                B0 = wave_allsum(B0);
+                B1 = wave_allsum(B1);
+                fxv = fxv + det_inv * (A11 * B0 - A01 * B1);
+                fyv = fyv + det_inv * (-A10 * B0 + A00 * B1);
+            }
+        }
+        if (lane == 0) {
+            fl[0] = fxv;
+            fl[1] = fyv;
+        }
+        // the window slice is reused by the next frame: its stores stay behind this frame's LDS reads
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
 }
 
@@ -906,9 +964,16 @@ extern "C" int hhsr_align_level_batch(const float* ref, int rh, int rw, int ref_
             fr.flow[k] = flows[n];
             fr.coarse[k] = coarse_flows ? reinterpret_cast<const float2*>(coarse_flows[n]) : nullptr;
         }
-        const dim3 g(hhsr_cdiv(ntiles, 4), nb);
-#define ALW(TS, R, L1) hipLaunchKernelGGL((k_align_wave<TS, R, L1>), g, b, l, s, ref, rh, rw, ref_pitch, hess, fr, mh, \
-                                          mw, mov_pitch, nx, ntiles, mode, n_iter, cny, cnx, rep, mult)
+        // One wave per tile walks the nb frames of the launch (reference tile, Hessian and geometry once per tile) where
+        // the grid still fills the GPU that way; below HHSR_ALIGN_LOOP_MIN_TILES = 24576 tiles one wave per (tile, frame):
+        // a launch of few workgroups only gets longer with 3 - 4 times longer waves.  Measured per 4-frame launch, loop
+        // against one wave per (tile, frame): <16, 1, true> 20 vs 8 us at 713 tiles, even at 16 k, -4.5 % at 20 k, -9 % at
+        // 41 k; <16, 2, false> +7 % at 16 k, even at 24 k; <8, 1> and <32, 1> ahead from 16 k (profiles/align_chunk_loop.txt)
+        // Not for r = 4: that instantiation has no register to spare for a frame loop (see the kernel).
+        const int fpw = (r != 4 && ntiles >= HHSR_ALIGN_LOOP_MIN_TILES) ? nb : 1;
+        const dim3 g(hhsr_cdiv(ntiles, 4), hhsr_cdiv(nb, fpw));
+#define ALW(TS, R, L1) hipLaunchKernelGGL((k_align_wave<TS, R, L1>), g, b, l, s, ref, rh, rw, ref_pitch, hess, fr, nb, fpw, \
+                                          mh, mw, mov_pitch, nx, ntiles, mode, n_iter, cny, cnx, rep, mult)
 #define ALW_R(TS, L1) do { if (r == 1) ALW(TS, 1, L1); else if (r == 2) ALW(TS, 2, L1); else ALW(TS, 4, L1); } while (0)
         if (metric == 0) {
             if (ts == 8) ALW_R(8, false);
