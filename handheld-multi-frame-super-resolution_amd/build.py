@@ -32,6 +32,7 @@ SOURCES = {
     "hhsr_io.hip": ["-ffp-contract=off"],
     "hhsr_post.hip": ["-ffp-contract=off"],
     "hhsr_tonemap.hip": ["-ffp-contract=off"],  # the Mertens weight maps are a decision stage (exact float32 association)
+    "hhsr_noise.hip": ["-ffp-contract=off"],    # the Monte-Carlo stream is stated without fused multiply-adds (hhsr.h)
 }
 
 

@@ -75,6 +75,10 @@ _SIGS = {
     "hhsr_mertens": [P, I, I, I, P, SZ, P, P, I, P],
     "hhsr_merge_burst": [PP, PP, PP, PP, I, I, I, I, I, I, I, P, P, U8P, D, I, I, P, P, P, I, I, I, I, I, P],
     "hhsr_merge_plan_query": [I, I, I, I, U8P, D, I, I, I, I, I, I, I, I, I32P, I],
+    "hhsr_noise_mc_levels": [D, D, I32P, I, I32P],
+    "hhsr_noise_mc_workspace": [I, I, SZP],
+    "hhsr_noise_mc": [P, I, D, D, I, C.c_uint64, P, P, P, SZ, P],
+    "hhsr_noise_curves_fill": [I32P, I, DP, DP, DP, DP],
     "hhsr_clock_probe": [P, L, P],
     "hhsr_merge_burst_chain": [PP, PP, PP, PP, I, I, I, I, I, I, I, P, P, U8P, D, I, I, P, P, P, I, I, P, I, P],
 }
@@ -85,6 +89,7 @@ MAX_FRAMES = 64
 MAX_BATCH = 8  # HHSR_MAX_BATCH: frames per launch of the batched front-end entry points
 MAX_EXPOSURES = 4  # HHSR_MAX_EXPOSURES: exposures per hhsr_post_expose / hhsr_mertens call
 GREY_INFO_LEN = 48  # HHSR_GREY_INFO_LEN: values of the record of hhsr_grey_plan_query / hhsr_grey_plan_info
+NOISE_MC_CHUNK = 2048  # HHSR_NOISE_MC_CHUNK: patch pairs per workgroup of hhsr_noise_mc
 MERGE_PLAN_LEN = 8  # HHSR_MERGE_PLAN_LEN: values of the record of hhsr_merge_plan_query
 MERGE_FAMILIES = ("generic", "tile", "x2_v1", "x2_mono", "x2", "x3")  # HHSR_MERGE_FAMILY_*: the record's [0]
 MERGE_GEOM_P2 = 1  # HHSR_MERGE_GEOM_P2: the record's [1]

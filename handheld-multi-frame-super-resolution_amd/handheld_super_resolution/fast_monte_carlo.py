@@ -6,7 +6,13 @@ clipped to [0, 1]; sigma_t = mean of the patches' standard deviation, d_t = mean
 means| (fast_monte_carlo.py:44-84).  Like the reference, only the brightness levels where clipping matters are
 simulated (within `tol` sigma of 0 or 1); in between sigma^2 and d^2 are linear in b and interpolated
 (:126-157, :160-214).  The reference uses an unseeded NumPy RNG on all CPU cores (seconds); here one torch
-generator on the device (milliseconds, reproducible)."""
+generator on the device (milliseconds, reproducible).
+
+engine="hip": the same estimator as ONE fused kernel of the C library (hhsr_noise_mc, include/hhsr.h: counter-based
+Philox stream, every sample generated, clipped and reduced in registers) — what a client of the C ABI without torch
+runs.  Its stream is not torch's, so its seeded values differ from engine="torch" by Monte-Carlo noise."""
+import ctypes
+
 import numpy as np
 import torch
 
@@ -51,8 +57,42 @@ def interp_MC(b_array, sigma_min, sigma_max, diff_min, diff_max):
     return np.sqrt(s2[1:-1]), np.sqrt(d2[1:-1])
 
 
-def run_fast_MC(alpha, beta, seed=0, device=None, n_patches=N_PATCHES):
-    """(std_curve, diff_curve): float64[1001] for brightness 0, 0.001, ..., 1 (fast_monte_carlo.py:160-214)."""
+def _run_fast_MC_hip(alpha, beta, seed, device, n_patches):
+    """levels -> hhsr_noise_mc -> one D2H of 2 n_levels doubles -> fill, all in the library."""
+    from . import _lib
+
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if dev.type != "cuda":
+        raise RuntimeError('run_fast_MC(engine="hip") needs a GPU device (the HIP path has no CPU fallback)')
+    levels = np.empty(N_BRIGHTNESS_LEVELS + 1, np.int32)
+    n_lv, nbytes = ctypes.c_int32(0), ctypes.c_size_t(0)
+    _lib.call("hhsr_noise_mc_levels", float(alpha), float(beta), levels.ctypes.data_as(_lib.I32P), levels.size,
+              ctypes.byref(n_lv))
+    levels = levels[:n_lv.value]
+    _lib.call("hhsr_noise_mc_workspace", levels.size, int(n_patches), ctypes.byref(nbytes))
+    with torch.cuda.device(dev):
+        lv_dev = torch.from_numpy(levels).to(dev)
+        out = torch.empty(2 * levels.size, dtype=torch.float64, device=dev)
+        ws = torch.empty(nbytes.value // 8, dtype=torch.float64, device=dev)
+        _lib.call("hhsr_noise_mc", _lib.ptr(lv_dev), levels.size, float(alpha), float(beta), int(n_patches),
+                  int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(out), ctypes.c_void_p(out.data_ptr() + 8 * levels.size),
+                  _lib.ptr(ws), nbytes, _lib.stream(dev))
+        host = out.cpu().numpy()  # (the one device-to-host copy; it waits for the two kernels)
+    sigmas, diffs = np.empty(N_BRIGHTNESS_LEVELS + 1), np.empty(N_BRIGHTNESS_LEVELS + 1)
+    as_dp = lambda a: a.ctypes.data_as(_lib.DP)  # noqa: E731
+    sig, dif = np.ascontiguousarray(host[:levels.size]), np.ascontiguousarray(host[levels.size:])
+    _lib.call("hhsr_noise_curves_fill", levels.ctypes.data_as(_lib.I32P), levels.size, as_dp(sig), as_dp(dif),
+              as_dp(sigmas), as_dp(diffs))
+    return sigmas, diffs
+
+
+def run_fast_MC(alpha, beta, seed=0, device=None, n_patches=N_PATCHES, engine="torch"):
+    """(std_curve, diff_curve): float64[1001] for brightness 0, 0.001, ..., 1 (fast_monte_carlo.py:160-214).
+    engine: "torch" (default: the element-wise torch estimator below) or "hip" (the fused kernel of the C library)."""
+    if engine == "hip":
+        return _run_fast_MC_hip(alpha, beta, seed, device, n_patches)
+    if engine != "torch":
+        raise ValueError(f'run_fast_MC: engine must be "torch" or "hip", got {engine!r}')
     n = N_BRIGHTNESS_LEVELS
     xmin, xmax = get_non_linearity_bound(alpha, beta, TOL)
     imin = int(np.ceil(xmin * n)) + 1

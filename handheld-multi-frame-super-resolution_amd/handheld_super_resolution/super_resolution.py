@@ -655,7 +655,9 @@ def process(burst_path, config):
     ImportError).  Noise curves: given in the burst, or ``config.noise_model.estimator``: "monte_carlo" (default — the
     reference's estimator run_fast_MC, super_resolution.py:252, whose curves include the clipping of the noisy samples
     to [0, 1]: near black and near saturation sigma_t and d_t are up to ~1.6x smaller than the un-clipped law; seeded by
-    ``config.noise_model.seed``, default 0, so process() is reproducible where the reference is not, D18) or
+    ``config.noise_model.seed``, default 0, so process() is reproducible where the reference is not, D18),
+    "monte_carlo_hip" (the same estimator as one fused kernel of the C library, hhsr_noise_mc: its own seeded stream,
+    stated in include/hhsr.h, so its curves differ from "monte_carlo" by Monte-Carlo noise) or
     "analytic" (the un-clipped limit, synthetic.noise_curves — what prepare_config() uses when called directly).
     After main(): the frame-count denoisers (``accumulated_robustness_denoiser.median / .gauss``), then
     ``postprocessing`` (colour matrix, unsharp mask, devignetting, gamma — ON by default like the reference's YAML; tone
@@ -714,12 +716,14 @@ def process(burst_path, config):
         brightness_src = None
     std_curve, diff_curve = burst.get("std_curve"), burst.get("diff_curve")
     alpha, beta = burst.get("alpha"), burst.get("beta")
-    if (std_curve is None or diff_curve is None) and config.noise_model.get("estimator", "monte_carlo") == "monte_carlo":
+    estimator = config.noise_model.get("estimator", "monte_carlo")
+    if (std_curve is None or diff_curve is None) and estimator in ("monte_carlo", "monte_carlo_hip"):
         from .fast_monte_carlo import run_fast_MC  # the reference's estimator (super_resolution.py:252), seeded
 
         if config.noise_model.get("alpha", None) is not None:
             alpha, beta = config.noise_model.alpha, config.noise_model.beta
-        std_curve, diff_curve = run_fast_MC(float(alpha), float(beta), seed=int(config.noise_model.get("seed", 0)))
+        std_curve, diff_curve = run_fast_MC(float(alpha), float(beta), seed=int(config.noise_model.get("seed", 0)),
+                                            engine="hip" if estimator == "monte_carlo_hip" else "torch")
     ref_for_stats = ref_raw if brightness_src is None else np.full((1, 1), brightness_src, np.float32)
     prepare_config(config, ref_for_stats, alpha, beta, burst["cfa_pattern"], burst["white_balance"],
                    int(burst.get("iso", 100)), std_curve, diff_curve,

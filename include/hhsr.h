@@ -514,6 +514,65 @@ int hhsr_post_expose(const float* image, float* tmp, int H, int W, const float* 
 int hhsr_mertens(const uint8_t* exposures, int n, int H, int W, void* workspace, size_t workspace_bytes,
                  float* weights_out, float* out, int smoothstep, void* stream);
 
+/* ---- noise curves of the robustness noise model (fast_monte_carlo.py; super_resolution.py:252) ------------------------
+ * std_curve / diff_curve, float64[1001] for brightness i / 1000, i = 0 .. 1000 — the tables hhsr_rob_sigma,
+ * hhsr_ref_planes and hhsr_rob_frame read — from the sensor's noise profile (alpha, beta): for every brightness draw
+ * n_patches pairs of 3 x 3 patches b + sqrt(alpha b + beta) N(0, 1) clipped to [0, 1]; sigma = mean over the pairs of
+ * the patches' mean standard deviation, d = mean |difference of the two patch means| (fast_monte_carlo.py:44-84).  The
+ * reference draws from an unseeded generator; here the stream is part of the contract (tests/noise_mc_ref.py is its
+ * NumPy form), so a value depends on (alpha, beta, n_patches, seed, i) alone:
+ *
+ * random words   Philox4x32-10.  key (k0, k1) = (seed & 0xffffffff, seed >> 32); counter (c0, c1, c2, c3) = (patch pair
+ *                p in 0 .. n_patches - 1, brightness index i, call k in 0 .. 4, 0) — the brightness INDEX, not its place
+ *                in `levels`.  Ten times: (c0, c1, c2, c3) <- (hi(0xCD9E8D57 c2) ^ c1 ^ k0, lo(0xCD9E8D57 c2),
+ *                hi(0xD2511F53 c0) ^ c3 ^ k1, lo(0xD2511F53 c0)) with hi / lo the halves of the 64-bit product, then
+ *                (k0, k1) <- (k0 + 0x9E3779B9, k1 + 0xBB67AE85) mod 2^32.  The call's words are x0 .. x3 = c0 .. c3.
+ * normals        per call two Box-Muller pairs, (x0, x1) then (x2, x3): u = ((x >> 8) + 0.5) 2^-24 for both words,
+ *                r = sqrt(-2 ln u_first), theta = 2 pi u_second, z = (r cos theta, r sin theta).  Call k gives normals
+ *                4k .. 4k + 3; of the 20 normals of a pair, 0 .. 8 are patch 1 (row major), 9 .. 17 patch 2, 18 and 19
+ *                are unused.
+ * patch pair     float32, no fused multiply-add, sums left to right, typed as the torch estimator of
+ *                fast_monte_carlo.regular_MC: b = float32(i / 1000) (the quotient in float64), s = sqrt(b float32(alpha) +
+ *                float32(beta)), p_j = min(max(b + s z_j, 0), 1); per patch m = (p_0 + .. + p_8) / 9,
+ *                sd = sqrt(((p_0 - m)^2 + .. + (p_8 - m)^2) / 9); per pair 0.5 (sd_1 + sd_2) and |m_1 - m_2|.  The
+ *                normals are float32 too (u, ln, sqrt, 2 pi u, cos, sin; precise logf / sincosf, not the fast intrinsics).
+ * accumulation   both per-pair values are widened to float64, summed over the pairs and divided by n_patches.  The
+ *                order of the additions is fixed — a workgroup of 256 threads owns a chunk of HHSR_NOISE_MC_CHUNK
+ *                consecutive pairs of one level (a thread every 256th of them, then wave shuffles, then the four waves
+ *                through LDS in ascending order) and stores one partial per (level, chunk); a second kernel adds a
+ *                level's partials in ascending chunk order.  No atomics: the same arguments give the same bits on every
+ *                run, whatever else the GPU does, and a level's value does not depend on which other levels are in the
+ *                launch or where it stands among them.  The order itself is not part of the contract (it moves the
+ *                result by float64 rounding only).
+ *
+ * hhsr_noise_mc_levels (host only, no HIP call): the brightness indices run_fast_MC simulates, ascending, into levels
+ *   (HOST int32[n]) and their number into *n_out: with (xmin, xmax) = get_non_linearity_bound(alpha, beta, tol = 3) —
+ *   xmin = 4.5 (alpha + sqrt(9 alpha^2 + 4 beta)), xmax = (B - sqrt(B^2 - 4 (1 + 9 beta))) / 2, B = 2 + 9 alpha, in
+ *   float64 — imin = ceil(1000 xmin) + 1 and imax = floor(1000 xmax) - 1: 0 .. imin and imax .. 1000, or all 1001 when
+ *   imin > 1000 or imax <= imin (the reference's fallback; also taken when a bound is NaN or imax > 999 — beta above about
+ *   alpha — where the reference raises).
+ *   *n_out is set even when n is too small (error -1 then: n = 1001 always suffices; levels may be NULL with n = 0).
+ * hhsr_noise_mc_workspace (host only): bytes of the partial sums, 2 n_levels ceil(n_patches / HHSR_NOISE_MC_CHUNK) doubles.
+ * hhsr_noise_mc: levels DEVICE int32[n_levels] in any order (an index outside 0 .. 1000 is clamped into it by the
+ *   kernel: the host cannot see it) -> sigma, diff DEVICE double[n_levels] in the order of levels.  Asynchronous on
+ *   `stream`: two launches, no allocation, copy or synchronisation, so it can be captured into a graph.  workspace:
+ *   DEVICE, 8-byte aligned, at least the bytes hhsr_noise_mc_workspace reports; its contents are scratch.
+ *   Error -1 (before any HIP call): a null pointer, n_levels outside 1 .. 1001, n_patches < 1, alpha or beta negative or
+ *   not finite, a misaligned pointer, a workspace that is too small.
+ * hhsr_noise_curves_fill (host only; every pointer HOST): std_curve[levels[k]] = sigma[k], diff_curve likewise; the
+ *   indices between the two simulated runs 0 .. imin and imax .. 1000 are interpolated as interp_MC /
+ *   run_fast_MC do (fast_monte_carlo.py:126-157, 200-212): for i = imin .. imax, BOTH ends included (their simulated values are
+ *   replaced), nb = (i / 1000 - (imin - 1) / 1000) / ((imax + 1) / 1000 - (imin - 1) / 1000) and
+ *   std_curve[i] = sqrt(nb (sigma_imax^2 - sigma_imin^2) + sigma_imin^2), diff_curve the same with d.  With all 1001 levels
+ *   given it is a copy.  Error -1: a level outside 0 .. 1000 or given twice, levels that are not 0 .. imin and imax .. 1000. */
+#define HHSR_NOISE_MC_CHUNK 2048  /* patch pairs per workgroup of hhsr_noise_mc */
+int hhsr_noise_mc_levels(double alpha, double beta, int32_t* levels, int n, int32_t* n_out);
+int hhsr_noise_mc_workspace(int n_levels, int n_patches, size_t* bytes);
+int hhsr_noise_mc(const int32_t* levels, int n_levels, double alpha, double beta, int n_patches, uint64_t seed,
+                  double* sigma, double* diff, void* workspace, size_t workspace_bytes, void* stream);
+int hhsr_noise_curves_fill(const int32_t* levels, int n_levels, const double* sigma, const double* diff,
+                           double* std_curve, double* diff_curve);
+
 /* ---- measurement support ------------------------------------------------------------------------------------------
  * Shader-clock probe: one wave that sleeps for `ticks_100mhz` ticks of the constant 100 MHz counter and stores
  * {shader cycles, 100 MHz ticks} at its start and end into out4 (DEVICE uint64[4]); launched on a side stream around a
