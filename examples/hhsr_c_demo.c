@@ -5,7 +5,8 @@
  *       -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$ORIGIN' -o hhsr_c_demo
  *
  * Normalises a synthetic uint16 Bayer frame (hhsr_normalize_raw_u16), builds one Gaussian pyramid level
- * (hhsr_gauss_decimate) and checks both against the same arithmetic done on the host.  Exit code 0 = match. */
+ * (hhsr_gauss_decimate), encodes the frame as uint8 / uint16 samples (hhsr_encode_image) and checks all three against the
+ * same arithmetic done on the host.  Exit code 0 = match. */
 #include <hip/hip_runtime_api.h>
 #include <math.h>
 #include <stdint.h>
@@ -64,6 +65,33 @@ int main(void) {
             if (d > worst) worst = d;
         }
     printf("normalise: bit-exact; pyramid level %dx%d: max abs diff vs float64 %.2e\n", h2, w2, worst);
+    /* integer output: the normalised frame (values up to 1.9: clipped) as uint8 with padded rows from an odd base, and
+     * as compact uint16, against the rule of hhsr.h written out on the host */
+    enum { ROW8 = W + 5, OFF8 = 3 };
+    static uint8_t enc8[OFF8 + H * ROW8];
+    static uint16_t enc16[H * W];
+    uint8_t* d_enc8;
+    uint16_t* d_enc16;
+    CHECK_HIP(hipMalloc((void**)&d_enc8, sizeof enc8));
+    CHECK_HIP(hipMalloc((void**)&d_enc16, sizeof enc16));
+    CHECK_HIP(hipMemset(d_enc8, 0xA5, sizeof enc8));
+    CHECK_HHSR(hhsr_encode_image(d_norm, H, W, 1, 1, d_enc8 + OFF8, 8, ROW8, NULL));
+    CHECK_HHSR(hhsr_encode_image(d_norm, H, W, 1, 1, d_enc16, 16, W * sizeof(uint16_t), NULL));
+    CHECK_HIP(hipMemcpy(enc8, d_enc8, sizeof enc8, hipMemcpyDeviceToHost));
+    CHECK_HIP(hipMemcpy(enc16, d_enc16, sizeof enc16, hipMemcpyDeviceToHost));
+    for (int i = 0; i < OFF8 + H * ROW8; ++i) {
+        const int y = (i - OFF8) / ROW8, x = (i - OFF8) % ROW8;
+        unsigned want = 0xA5; /* in front of the base, between the rows: untouched */
+        if (i >= OFF8 && x < W) {
+            float v = norm_host[y * W + x];
+            v = v != v ? 0.f : (v < 0.f ? 0.f : (v > 1.f ? 1.f : v));
+            want = (unsigned)rintf(v * 255.f); /* half to even */
+            if (enc16[y * W + x] != (unsigned)rintf(v * 65535.f)) { fprintf(stderr, "uint16 mismatch at %d,%d\n", y, x); return 1; }
+        }
+        if (enc8[i] != want) { fprintf(stderr, "uint8 mismatch at byte %d: %u vs %u\n", i, enc8[i], want); return 1; }
+    }
+    printf("encode: uint8 (rows of %d bytes from base + %d) and uint16 match the host rule, padding untouched\n", ROW8, OFF8);
+    hipFree(d_enc8); hipFree(d_enc16);
     /* argument errors come back as codes + messages, never as exceptions */
     if (hhsr_gauss_decimate(d_norm, H, W, W, d_lvl, w2, 3, taps, NT, NULL) == 0) return 1;
     printf("rejected factor 3: %s\n", hhsr_last_error());

@@ -79,6 +79,8 @@ _SIGS = {
     "hhsr_noise_mc_workspace": [I, I, SZP],
     "hhsr_noise_mc": [P, I, D, D, I, C.c_uint64, P, P, P, SZ, P],
     "hhsr_noise_curves_fill": [I32P, I, DP, DP, DP, DP],
+    "hhsr_encode_image": [P, I, I, I, I, P, I, SZ, P],
+    "hhsr_encode_mask": [P, I, I, I, P, I, I, SZ, P],
     "hhsr_clock_probe": [P, L, P],
     "hhsr_merge_burst_chain": [PP, PP, PP, PP, I, I, I, I, I, I, I, P, P, U8P, D, I, I, P, P, P, I, I, P, I, P],
 }

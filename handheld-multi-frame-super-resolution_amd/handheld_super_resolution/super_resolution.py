@@ -662,11 +662,19 @@ def process(burst_path, config):
     After main(): the frame-count denoisers (``accumulated_robustness_denoiser.median / .gauss``), then
     ``postprocessing`` (colour matrix, unsharp mask, devignetting, gamma — ON by default like the reference's YAML; tone
     mapping raises NotImplementedError) and the EXIF orientation, all on the GPU (utils_image.py, raw2rgb.py); only the
-    finished image is copied to the host."""
+    finished image is copied to the host.  ``config.output = {"dtype": "uint8" | "uint16"}`` (optional; absent or "float32":
+    the float32 image as above): the finished, oriented image is quantised on the GPU — rint(clip(nan_to_num(x), 0, 1) * M),
+    half to even, M = 255 / 65535: skimage's img_as_ubyte and the reference's 16-bit TIFF rule (hhsr_encode_image) — and only
+    the integer image is copied; the result is an ndarray of that dtype, [sH, sW, 3] or, with ``mode: grey``, [sH, sW]
+    (channel 0).  With ``robustness.save_mask`` as well, ``debug_dict["robustness mask"]`` is the reference's mask image:
+    uint8 [sH, sW], accumulated robustness / number of comparison frames, nearest neighbour (hhsr_encode_mask)."""
     import os
 
     from .utils_dng import infer_width, load_dng_burst, normalize_burst, normalize_packed
 
+    out_dtype = str((config.get("output", None) or {}).get("dtype", "float32"))  # optional section, not in the reference schema
+    if out_dtype not in ("float32", "uint8", "uint16"):
+        raise ValueError(f"config.output.dtype {out_dtype!r}: float32, uint8 or uint16")
     if isinstance(burst_path, (str, os.PathLike)) and str(burst_path).endswith(".npz"):
         burst = dict(np.load(burst_path))
     elif isinstance(burst_path, (str, os.PathLike)):
@@ -751,7 +759,16 @@ def process(burst_path, config):
                                   orientation=ori, restated_tonemapping=True)
     else:
         out = apply_orientation(out, ori)
-    output_image = out.cpu().numpy()
-    if "accumulated robustness" in debug_dict:
-        debug_dict["accumulated robustness"] = apply_orientation(debug_dict["accumulated robustness"], ori).cpu().numpy()
+    acc_oriented = apply_orientation(debug_dict["accumulated robustness"], ori) if "accumulated robustness" in debug_dict else None
+    if out_dtype == "float32":
+        output_image = out.cpu().numpy()
+    else:  # integer output: encoded on the device, 3 or 6 instead of 12 bytes per pixel cross the host link
+        from .utils_image import encode_image, robustness_mask
+
+        output_image = encode_image(out, out_dtype, channels=1 if config.mode == "grey" else None).cpu().numpy()
+        if acc_oriented is not None and config.robustness.save_mask:  # the reference's `.rob.png` (run_handheld.py:153-159)
+            debug_dict["robustness mask"] = robustness_mask(acc_oriented, max(1, len(raw_comp)),  # (no comparison frame: the map is 0)
+                                                            output_image.shape[:2]).cpu().numpy()
+    if acc_oriented is not None:
+        debug_dict["accumulated robustness"] = acc_oriented.cpu().numpy()
     return output_image, debug_dict

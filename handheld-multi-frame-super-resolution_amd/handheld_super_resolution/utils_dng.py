@@ -200,3 +200,55 @@ def load_dng_burst(burst_path):
         xyz2cam = np.array([x.decimal() for x in tags["Image Tag 0xC621"].values]).reshape(3, 3).astype(np.float32)
     stack = normalize_burst(np.stack(frames), black_levels, white_level, white_balance, cfa)
     return stack[0], stack[1:], iso, tags, cfa, xyz2cam, white_balance, paths[0]
+
+
+TIFF_MAX_BYTES = 2 ** 32 - 1  # classic TIFF: 32-bit offsets
+
+
+def save_as_tiff(int_im, outpath):
+    """uint8 / uint16 ndarray [H, W] or [H, W, 3] -> baseline TIFF (reference utils_dng.py:327-341, which writes it through
+    imageio with bigtiff=False): little-endian, uncompressed, one strip, chunky, standard library only.  A path that does
+    not end in .tif / .tiff gets the suffix .tif, as upstream.  RuntimeError when the file would pass classic TIFF's 4 GiB,
+    like the reference.  save_as_dng is not part of this build: it needs exiftool and dng_validate."""
+    import os
+    import struct
+
+    a = np.asarray(int_im)
+    if a.dtype not in (np.uint8, np.uint16) or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3) or a.size == 0:
+        raise ValueError(f"save_as_tiff expects uint8 / uint16 [H, W] or [H, W, 3], got {a.dtype} {a.shape}")
+    path = os.fspath(outpath)
+    if os.path.splitext(path)[1].lower() not in (".tif", ".tiff"):
+        path = os.path.splitext(path)[0] + ".tif"
+    H, W = a.shape[:2]
+    spp, bits = (3 if a.ndim == 3 else 1), 8 * a.dtype.itemsize
+    nbytes = _tiff_pixel_bytes(a)
+    SHORT, LONG, RATIONAL = 3, 4, 5
+    # header (8) | BitsPerSample x 3 (6, RGB only) + pad (2) | XResolution, YResolution (16) | IFD | pixels
+    bps_off, res_off, ifd_off = 8, 16, 32
+    tags = [(256, LONG, 1, W), (257, LONG, 1, H), (258, SHORT, spp, bps_off if spp == 3 else bits), (259, SHORT, 1, 1),
+            (262, SHORT, 1, 2 if spp == 3 else 1), (273, LONG, 1, 0), (277, SHORT, 1, spp), (278, LONG, 1, H),
+            (279, LONG, 1, nbytes), (282, RATIONAL, 1, res_off), (283, RATIONAL, 1, res_off + 8), (284, SHORT, 1, 1),
+            (296, SHORT, 1, 2)]
+    data_off = ifd_off + 2 + 12 * len(tags) + 4
+    if data_off + nbytes > TIFF_MAX_BYTES:
+        raise RuntimeError(f"{os.path.basename(path)!r}: {data_off + nbytes} bytes are too large for a classic TIFF, whose "
+                           f"offsets are 32-bit (4 GiB); BigTIFF is not written.")
+    head = struct.pack("<2sHI", b"II", 42, ifd_off) + struct.pack("<4H", bits, bits, bits, 0)
+    head += struct.pack("<4I", 72, 1, 72, 1) + struct.pack("<H", len(tags))
+    for tag, typ, count, value in tags:
+        if tag == 273:
+            value = data_off
+        if typ == SHORT and count == 1:
+            head += struct.pack("<HHIHH", tag, typ, count, value, 0)
+        else:
+            head += struct.pack("<HHII", tag, typ, count, value)
+    head += struct.pack("<I", 0)  # no further IFD
+    assert len(head) == data_off
+    with open(path, "wb") as f:
+        f.write(head)
+        f.write(np.ascontiguousarray(a.astype("<u2") if a.dtype == np.uint16 else a).tobytes())
+
+
+def _tiff_pixel_bytes(a):
+    """Bytes of the one strip (its own function: the 4 GiB refusal is tested without allocating 4 GiB)."""
+    return int(a.size) * a.dtype.itemsize

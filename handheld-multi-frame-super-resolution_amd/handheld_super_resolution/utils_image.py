@@ -242,6 +242,84 @@ def apply_orientation(img, ori):
     return t(img).contiguous()
 
 
+# ---- integer output (reference run_handheld.py:132-159, utils_dng.py:208-215) ------------------------------------------
+OUTPUT_DTYPES = {"uint8": 8, "uint16": 16}
+
+
+def _output_bits(dtype):
+    name = dtype if isinstance(dtype, str) else str(np.dtype(dtype) if not isinstance(dtype, torch.dtype) else dtype)
+    name = name.replace("torch.", "")
+    if name not in OUTPUT_DTYPES:
+        raise ValueError(f"integer output dtype {dtype!r}: one of {sorted(OUTPUT_DTYPES)}")
+    return name, OUTPUT_DTYPES[name]
+
+
+def encode_image(img, dtype, channels=None):
+    """Device float32 [H, W, 3] or [H, W] -> device uint8 / uint16 of the same shape: rint(clip(nan_to_num(x), 0, 1) * M),
+    half to even, M = 255 / 65535 (hhsr_encode_image; skimage's img_as_ubyte / the reference's 16-bit quantisation).
+    `channels=1` of an [H, W, 3] image: channel 0 alone as [H, W] (`mode: grey`).  The kernel reads a compact image: a
+    strided view goes through _lib.f32c, i.e. is copied first (not optimised).  process() never passes one — raw2rgb.postprocess
+    stores the oriented image compactly, and with post-processing off apply_orientation has already made the rotated
+    image contiguous, which is that same copy, one step earlier."""
+    name, bits = _output_bits(dtype)
+    if not (torch.is_tensor(img) and img.is_cuda):
+        raise RuntimeError("encode_image expects a tensor on the GPU (the HIP path has no CPU fallback)")
+    src = _lib.f32c(img)
+    if src.dim() not in (2, 3) or (src.dim() == 3 and src.shape[2] not in (1, 3)):
+        raise ValueError(f"encode_image expects [H, W] or [H, W, 3], got {tuple(src.shape)}")
+    H, W = src.shape[:2]
+    ch = 1 if src.dim() == 2 else src.shape[2]
+    och = ch if channels is None else int(channels)
+    if och not in (ch, 1):
+        raise ValueError(f"channels={channels}: {ch} (all of them) or 1 (channel 0)")
+    shape = (H, W) if (och == 1 and (src.dim() == 2 or channels is not None)) else (H, W, och)
+    out = torch.empty(shape, dtype=getattr(torch, name), device=src.device)
+    _lib.call("hhsr_encode_image", _lib.ptr(src), H, W, ch, och, _lib.ptr(out), bits, W * och * bits // 8,
+              _lib.stream(src.device))
+    return out
+
+
+def robustness_mask(acc_r, n_comp, out_shape):
+    """Oriented accumulated robustness, device float32 [ah, aw] -> device uint8 [mH, mW]: acc / n_comp, nearest-neighbour
+    index (y * ah) // mH, quantised like encode_image (hhsr_encode_mask; the reference's `.rob.png`, one grey channel)."""
+    if not (torch.is_tensor(acc_r) and acc_r.is_cuda):
+        raise RuntimeError("robustness_mask expects a tensor on the GPU (the HIP path has no CPU fallback)")
+    acc = _lib.f32c(acc_r)
+    if acc.dim() != 2:
+        raise ValueError(f"robustness_mask expects [ah, aw], got {tuple(acc.shape)}")
+    mH, mW = (int(v) for v in out_shape)
+    out = torch.empty((mH, mW), dtype=torch.uint8, device=acc.device)
+    _lib.call("hhsr_encode_mask", _lib.ptr(acc), acc.shape[0], acc.shape[1], int(n_comp), _lib.ptr(out), mH, mW, mW,
+              _lib.stream(acc.device))
+    return out
+
+
+def save_png(arr, path):
+    """uint8 / uint16 ndarray [H, W] or [H, W, 3] -> PNG file, standard library only: filter type 0 on every row, 16-bit
+    samples big-endian, zlib level 1 (a 48 MP image is written for its content, not its size)."""
+    import struct
+    import zlib
+
+    a = np.asarray(arr)
+    if a.dtype not in (np.uint8, np.uint16) or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3) or a.size == 0:
+        raise ValueError(f"save_png expects uint8 / uint16 [H, W] or [H, W, 3], got {a.dtype} {a.shape}")
+    H, W = a.shape[:2]
+    rows = np.ascontiguousarray(a.astype(">u2") if a.dtype == np.uint16 else a).reshape(H, -1).view(np.uint8)
+    raw = np.zeros((H, rows.shape[1] + 1), np.uint8)  # byte 0 of a row: its filter type
+    raw[:, 1:] = rows
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+
+    ihdr = struct.pack(">IIBBBBB", W, H, 8 * a.dtype.itemsize, 2 if a.ndim == 3 else 0, 0, 0, 0)
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", ihdr))
+        data = zlib.compress(raw.tobytes(), 1)
+        for i in range(0, len(data), 1 << 30):  # (a chunk's length is a 31-bit field)
+            f.write(chunk(b"IDAT", data[i:i + (1 << 30)]))
+        f.write(chunk(b"IEND", b""))
+
+
 def _frame_count_denoise(image, r_acc, config, kind, strength, scale, half_index, mode=None):
     # `mode: grey` (monochrome sensors): the reference indexes the accumulated robustness with int(round(y / scale))
     # (utils_image.py:203-204, 260-261) instead of the Bayer branch's half-resolution index.  Upstream reads `mode` (and

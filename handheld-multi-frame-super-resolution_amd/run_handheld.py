@@ -1,0 +1,77 @@
+"""Command line of the burst super-resolution (the reference's run_handheld.py flags):
+
+    python run_handheld.py --impath burst.npz --outpath out.png [--config my.yaml] [key=value ...]
+
+--impath   a burst in an .npz file (the keys process() documents), or a folder of .dng files where rawpy + exifread exist
+--outpath  .png: 8-bit PNG;  .tif / .tiff: 16-bit uncompressed TIFF (post-processing as configured);  .dng: not built —
+           the reference's DNG export runs exiftool and dng_validate on such a TIFF
+--config   a YAML file merged over the defaults (config.DEFAULTS)
+key=value  overrides, e.g. scale=2 robustness.save_mask=false; the values are read as YAML scalars, never evaluated
+
+The image is quantised on the GPU (config.output.dtype, hhsr_encode_image) and written with the standard library
+(utils_image.save_png, utils_dng.save_as_tiff).  With robustness.save_mask the accumulated-robustness mask goes to
+<outpath stem>.rob.png like upstream."""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+
+def parse_args(argv=None):
+    parser = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    parser.add_argument("--config", type=str, help="YAML file whose keys are merged over the built-in defaults")
+    parser.add_argument("--impath", type=str, required=True, help="burst to process: an .npz file, or a folder of .dng frames")
+    parser.add_argument("--outpath", type=str, required=True, help="file to write: .png (8 bits) or .tif / .tiff (16 bits)")
+    parser.add_argument("overrides", nargs="*", help="dotted configuration keys set from the command line, e.g. scale=2 "
+                                                     "robustness.save_mask=false (values are YAML scalars)")
+    return parser.parse_args(argv)
+
+
+def build_config(args):
+    """Defaults, then --config, then the key=value overrides, then the output dtype the file type asks for."""
+    from handheld_super_resolution.config import OmegaConf, default_config
+
+    config = default_config()
+    if args.config:
+        config = OmegaConf.merge(config, OmegaConf.load(args.config))
+    for item in args.overrides:
+        if "=" not in item:
+            raise ValueError(f"override {item!r}: expected key=value")
+    if args.overrides:
+        config = OmegaConf.merge(config, OmegaConf.from_dotlist(args.overrides))
+    suffix = os.path.splitext(args.outpath)[1].lower()
+    if suffix == ".dng":
+        raise NotImplementedError("DNG output is not part of this build: the reference's save_as_dng rewrites a 16-bit TIFF "
+                                  "with the external tools exiftool and dng_validate. Ask for .tif (the same samples) instead.")
+    if suffix not in (".png", ".tif", ".tiff"):
+        raise ValueError(f"--outpath {args.outpath!r}: .png (8 bits), .tif / .tiff (16 bits)")
+    config.output = {"dtype": "uint8" if suffix == ".png" else "uint16"}
+    noise = config.noise_model
+    if (noise.get("alpha", None) is None) != (noise.get("beta", None) is None):
+        raise ValueError("noise_model.alpha and noise_model.beta describe one noise profile: set both or neither")
+    return config
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    config = build_config(args)
+
+    from handheld_super_resolution import process
+    from handheld_super_resolution.utils_dng import save_as_tiff
+    from handheld_super_resolution.utils_image import save_png
+
+    image, debug_dict = process(args.impath, config)
+    if config.verbose >= 1:
+        print(f"writing {args.outpath} ({image.dtype}, {' x '.join(str(n) for n in image.shape)})")
+    if image.dtype.itemsize == 1:
+        save_png(image, args.outpath)
+    else:
+        save_as_tiff(image, args.outpath)
+    if config.robustness.save_mask and debug_dict.get("robustness mask", None) is not None:
+        save_png(debug_dict["robustness mask"], os.path.splitext(args.outpath)[0] + ".rob.png")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -573,6 +573,44 @@ int hhsr_noise_mc(const int32_t* levels, int n_levels, double alpha, double beta
 int hhsr_noise_curves_fill(const int32_t* levels, int n_levels, const double* sigma, const double* diff,
                            double* std_curve, double* diff_curve);
 
+/* ---- integer output (run_handheld.py:132-159; utils_dng.py:208-215): the finished image as the samples a file holds ------
+ * The reference copies the float32 image to the host and quantises it there: nan_to_num, clip(0, 1), then skimage
+ * img_as_ubyte for a PNG or round(x 65535) for the 16-bit TIFF of its DNG export.  Here the device image is encoded
+ * and only the integer samples cross the host link (3 or 6 instead of 12 bytes per RGB pixel).  One rule for both widths,
+ * in float32 without contraction — the rule hhsr_post_expose applies to its exposures:
+ *
+ *   v = x, NaN -> 0 (+-inf behave as +-FLT_MAX);  v = min(max(v, 0), 1);  p = v * M, M = 255 or 65535, ONE float32
+ *   multiply rounded once;  q = rint(p), half to even;  sample = q as uint8 / uint16 (0 <= q <= M always).
+ *
+ * tests/output_ref.py is its NumPy form.  It equals img_as_ubyte and utils_dng.py:212-215 on float32 input.
+ *
+ * hhsr_encode_image: image DEVICE float32, compact [H][W][channels], channels 1 or 3, 4-byte aligned.  out_channels ==
+ *   channels, or 1: channel 0 alone (the `mode: grey` result, whose channels 1 and 2 are NaN).  bits 8 or 16.  Row y of the
+ *   result starts at (char*)out + y * out_row_bytes and holds W * out_channels samples; the bytes between the end of a row
+ *   and the start of the next are never written, nor is anything else outside the rows.  out is aligned to its sample
+ *   size only (any byte for uint8); out_row_bytes is any value that holds a row.  The result does not depend on
+ *   alignment or stride; the time does: every lane loads float4 and stores 16 bytes wherever the output is 16-byte
+ *   aligned — a compact output (out_row_bytes == W * out_channels * bits / 8) is ONE run over the whole image, a padded
+ *   one a run per row; the fewer than 16 bytes before and behind the aligned part of a run are stored sample by sample.
+ *   With out_channels != channels, or an image that is not 16-byte aligned where the aligned part of a run begins, the
+ *   loads are dwords; with 16 bits and an odd out_row_bytes every other row starts on an odd byte and is stored byte by
+ *   byte.  Sample and byte indices are 64-bit; the launch has one workgroup per 4096 output bytes of a run.
+ *   Error -1, before any HIP call: a null image or out, H or W <= 0, bits not 8 or 16, channels not 1 or 3, out_channels
+ *   neither channels nor 1, out_row_bytes < W * out_channels * bits / 8 (or so large that the last row's end
+ *   overflows), an image off 4 bytes or a 16-bit out off 2, out overlapping image, more than INT32_MAX workgroups (a
+ *   compact uint8 image beyond 8.7e12 samples).
+ * hhsr_encode_mask: the robustness mask of run_handheld.py:153-159 — acc_r DEVICE float32 [ah][aw], the accumulated
+ *   robustness already oriented, -> out uint8 [mH][mW], rows out_row_bytes apart (>= mW; no alignment):
+ *   out[y][x] = rule8(acc_r[min((y ah) / mH, ah - 1)][min((x aw) / mW, aw - 1)] / float32(n_comp)), integer division of
+ *   64-bit products, the float32 division before the rule.  Upstream replicates three channels and resizes with OpenCV's
+ *   INTER_NEAREST; OpenCV is not part of this build: the index rule above is the contract, it is OpenCV's for integer
+ *   ratios, and it has not been compared with a cv2 run (PARITY.md).  Error -1: a null pointer, a size <= 0, n_comp < 1,
+ *   out_row_bytes < mW, a misaligned acc_r, out overlapping acc_r, mH > 262140. */
+int hhsr_encode_image(const float* image, int H, int W, int channels, int out_channels, void* out, int bits,
+                      size_t out_row_bytes, void* stream);
+int hhsr_encode_mask(const float* acc_r, int ah, int aw, int n_comp, uint8_t* out, int mH, int mW, size_t out_row_bytes,
+                     void* stream);
+
 /* ---- measurement support ------------------------------------------------------------------------------------------
  * Shader-clock probe: one wave that sleeps for `ticks_100mhz` ticks of the constant 100 MHz counter and stores
  * {shader cycles, 100 MHz ticks} at its start and end into out4 (DEVICE uint64[4]); launched on a side stream around a
