@@ -258,6 +258,28 @@ def test_post_path_golden(golden):
                                         sharpening=None, xyz2cam=np.zeros((3, 3))), g["pp_zero_ccm"], rtol=0, atol=5e-7)
 
 
+def test_post_edges_golden(golden):
+    """The post path at its borders against outputs of the reference's own functions (tools/refsim stage "post_edges"):
+    median denoiser with tied and NaN samples, integer robustness, radius 7, `mode: grey`, scale 1.5, one row / column,
+    a radius of exactly 2.5 (tolerance 0: the output is one of the samples); postprocess without sharpening at one row,
+    one column, one pixel and two rows (1e-6)."""
+    import post_cases as pc
+    from oracle import post
+
+    g = golden("post_edges")
+    assert np.isnan(g["med_in"]).sum() == 3 and len(np.unique(g["med_in"][~np.isnan(g["med_in"])])) == 6
+    for tag in pc.GOLDEN_MEDIANS:
+        img, racc, cfg, scale, half, want = pc.golden_median_case(g, tag)
+        got = post.frame_count_denoising_median(img, racc, cfg, scale, half)
+        assert np.array_equal(got, want, equal_nan=True), tag
+    kw = dict(do_color_correction=True, do_tonemapping=False, sharpening={"enabled": False}, do_devignette=True,
+              xyz2cam=g["pp_xyz2cam"])
+    for h, w in pc.GOLDEN_POST_SHAPES:
+        pin = g[f"pp_{h}x{w}_in"]
+        assert_close(post.postprocess(pin, do_gamma=False, **kw), g[f"pp_{h}x{w}_linear"], 0, 1e-6, f"linear {h}x{w}")
+        assert_close(post.postprocess(pin, do_gamma=True, **kw), g[f"pp_{h}x{w}_gamma"], 0, 1e-6, f"gamma {h}x{w}")
+
+
 def test_post_gauss_and_unsharp_known_answers():
     """Oracle-only parts of the post path: the gauss denoiser (upstream cannot run it) and the unsharp mask (restated
     through scipy.ndimage.gaussian_filter, the routine skimage.filters.unsharp_mask calls)."""

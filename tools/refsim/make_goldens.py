@@ -516,6 +516,61 @@ def stage_post():
     save("post", **out)
 
 
+POST_EDGE_SHAPES = [(1, 7), (7, 1), (1, 1), (2, 9), (5, 70)]  # postprocess: one row / column / pixel, fewer rows than a tile
+
+
+def stage_post_edges():
+    """Border and degenerate cases of the step after the hot path, all executed upstream code (fixture post_edges.npz;
+    stage_post and post.npz stay as they are): the median frame-count denoiser with tied and NaN samples, integer
+    accumulated robustness, radius up to 7 (the 225-sample window), `mode: grey`, a non-integer scale, images one pixel
+    high / wide and a radius that is an exact half (2.5 -> 2, half to even); raw2rgb.postprocess without sharpening on
+    images of one row, one column, one pixel and two rows."""
+    from handheld_super_resolution import utils_image as ui
+    from handheld_super_resolution import raw2rgb
+
+    rng = np.random.default_rng(177)
+    out = {}
+
+    def median(tag, img, racc, radius_max, scale, mode="bayer"):
+        cfg = cfgmod.Config({"enabled": True, "radius_max": radius_max, "max_frame_count": 8, "mode": mode, "scale": scale})
+        res = npy(ui.frame_count_denoising_median(cuda.to_device(img.copy()), cuda.to_device(racc.copy()), cfg).copy_to_host())
+        out[f"{tag}_racc"], out[f"{tag}_out"] = racc, res
+        out[f"{tag}_par"] = np.array([radius_max, 8, scale, mode == "grey"], np.float64)  # radius_max, mfc, scale, grey
+
+    # 14 x 18 x 3, samples on 6 levels of 1/8 (ties everywhere), three NaN samples (corner, interior, corner)
+    H, W = 14, 18
+    img = (rng.integers(0, 6, (H, W, 3)) / 8.0).astype(np.float32)
+    img[0, 0, 0] = img[6, 9, 1] = img[13, 17, 2] = np.nan
+    out["med_in"] = img
+    racc7 = rng.integers(0, 10, (7, 9)).astype(np.float64)  # integers 0 .. 9 with max_frame_count 8: radius 7 .. 0
+    assert set(np.unique(racc7)) == set(range(10))
+    median("med_r7_bayer", img, racc7, 7, 2, "bayer")
+    median("med_r7_grey", img, racc7, 7, 2, "grey")
+    median("med_s15", img, rng.integers(0, 10, (10, 12)).astype(np.float64), 3, 1.5)
+    # radius_max 5 and r = 4: radius = round(2.5) = 2 (Python's round: half to even), not 3
+    racc5 = rng.integers(0, 10, (7, 9)).astype(np.float64)
+    yy = np.rint((np.arange(H) - 0.5) / 4).astype(int).clip(0)
+    xx = np.rint((np.arange(W) - 0.5) / 4).astype(int).clip(0)
+    assert (5 * (8 - np.minimum(racc5[np.ix_(yy, xx)], 8)) / 8 == 2.5).any(), "no pixel reads the tie r = 4"
+    median("med_tie", img, racc5, 5, 2)
+    # one row / one column: robustness all zero, radius 3 everywhere
+    out["med_row_in"] = (rng.integers(0, 6, (1, 9, 3)) / 8.0).astype(np.float32)
+    out["med_col_in"] = (rng.integers(0, 6, (9, 1, 3)) / 8.0).astype(np.float32)
+    median("med_row", out["med_row_in"], np.zeros((1, 3)), 3, 2)
+    median("med_col", out["med_col_in"], np.zeros((3, 1)), 3, 2)
+
+    # postprocess without sharpening: colour matrix + devignetting, without and with gamma
+    xyz2cam = np.array([[1.0234, -0.2969, -0.2266], [-0.5625, 1.6328, -0.0469], [-0.0703, 0.2188, 0.6406]], np.float32)
+    out["pp_xyz2cam"] = xyz2cam
+    off = cfgmod.Config({"enabled": False})
+    for h, w in POST_EDGE_SHAPES:
+        pimg = (rng.random((h, w, 3)) * 1.2 - 0.1).astype(np.float32)
+        out[f"pp_{h}x{w}_in"] = pimg
+        out[f"pp_{h}x{w}_linear"] = raw2rgb.postprocess(None, pimg.copy(), True, False, False, off, True, xyz2cam)
+        out[f"pp_{h}x{w}_gamma"] = raw2rgb.postprocess(None, pimg.copy(), True, False, True, off, True, xyz2cam)
+    save("post_edges", **out)
+
+
 def stage_grey_mode():
     """`mode: grey` (monochrome sensors): the reference's own estimate_kernels / init_robustness / compute_robustness /
     merge / merge_ref on one-channel frames, and main() end to end (128x128, 3 frames, x2, Ts=16, all-L2)."""
@@ -704,7 +759,7 @@ def stage_frontend():
 STAGES = {
     "frontend": stage_frontend,
     "grey_mode": stage_grey_mode,
-    "post": stage_post,
+    "post": stage_post, "post_edges": stage_post_edges,
     "grey": stage_grey, "downsample": stage_downsample, "hessian": stage_hessian, "bm_l2": stage_bm_l2,
     "ica": stage_ica, "upscale": stage_upscale, "kernels": stage_kernels, "robustness": stage_robustness,
     "merge": stage_merge, "params": stage_params, "e2e": stage_e2e, "e2e_x1": stage_e2e_x1,
