@@ -6,7 +6,8 @@
  *
  * Normalises a synthetic uint16 Bayer frame (hhsr_normalize_raw_u16), builds one Gaussian pyramid level
  * (hhsr_gauss_decimate), encodes the frame as uint8 / uint16 samples (hhsr_encode_image) and checks all three against the
- * same arithmetic done on the host.  Exit code 0 = match. */
+ * same arithmetic done on the host; then codes the frame as a baseline JPEG (hhsr_jpeg_header, _workspace, _dct, _entropy)
+ * and, given a path as its argument, writes the file there.  Exit code 0 = match. */
 #include <hip/hip_runtime_api.h>
 #include <math.h>
 #include <stdint.h>
@@ -18,7 +19,7 @@
 #define CHECK_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); return 2; } } while (0)
 #define CHECK_HHSR(x) do { int rc_ = (x); if (rc_) { fprintf(stderr, "%s -> %d: %s\n", #x, rc_, hhsr_last_error()); return 3; } } while (0)
 
-int main(void) {
+int main(int argc, char** argv) {
     enum { H = 64, W = 96, F = 2, NT = 4 * F + 1 };
     static uint16_t counts[H * W];
     static float norm_host[H * W], norm_dev[H * W];
@@ -92,6 +93,45 @@ int main(void) {
     }
     printf("encode: uint8 (rows of %d bytes from base + %d) and uint16 match the host rule, padding untouched\n", ROW8, OFF8);
     hipFree(d_enc8); hipFree(d_enc16);
+    /* JPEG output: the same frame as a one-component baseline file through the four entry points — header on the host,
+     * coefficients and scan on the device, the length word read back, header || scan || EOI written to argv[1] if given */
+    {
+        enum { QUALITY = 90, RI = 8 };
+        uint8_t head[1024];
+        size_t head_len = 0, coef_bytes = 0, scratch_bytes = 0, max_scan = 0;
+        CHECK_HHSR(hhsr_jpeg_header(H, W, 1, QUALITY, RI, head, sizeof head, &head_len));
+        CHECK_HHSR(hhsr_jpeg_workspace(H, W, 1, RI, &coef_bytes, &scratch_bytes, &max_scan));
+        if (head_len < 300 || head[0] != 0xFF || head[1] != 0xD8 || head[2] != 0xFF || head[3] != 0xE0 ||
+            head[head_len - 1] != 0 || head[head_len - 2] != 63) { fprintf(stderr, "jpeg header is malformed\n"); return 1; }
+        const size_t capacity = (size_t)2 * H * W; /* the first guess of the Python layer; max_scan always suffices */
+        int16_t* d_coef;
+        void* d_scratch;
+        uint8_t* d_scan;
+        uint64_t *d_len, len = 0;
+        CHECK_HIP(hipMalloc((void**)&d_coef, coef_bytes));
+        CHECK_HIP(hipMalloc(&d_scratch, scratch_bytes));
+        CHECK_HIP(hipMalloc((void**)&d_scan, capacity));
+        CHECK_HIP(hipMalloc((void**)&d_len, sizeof len));
+        CHECK_HHSR(hhsr_jpeg_dct(d_norm, H, W, 1, 1, QUALITY, d_coef, coef_bytes, NULL));
+        CHECK_HHSR(hhsr_jpeg_entropy(d_coef, H, W, 1, RI, d_scratch, scratch_bytes, d_scan, capacity, d_len, NULL));
+        CHECK_HIP(hipMemcpy(&len, d_len, sizeof len, hipMemcpyDeviceToHost));
+        if (len == 0 || len > capacity || capacity > max_scan) { fprintf(stderr, "jpeg scan of %llu bytes, capacity %zu, bound %zu\n", (unsigned long long)len, capacity, max_scan); return 1; }
+        uint8_t* scan = (uint8_t*)malloc((size_t)len + 2);
+        CHECK_HIP(hipMemcpy(scan, d_scan, (size_t)len, hipMemcpyDeviceToHost));
+        scan[len] = 0xFF; scan[len + 1] = 0xD9; /* EOI */
+        if (argc > 1) {
+            FILE* f = fopen(argv[1], "wb");
+            if (!f || fwrite(head, 1, head_len, f) != head_len || fwrite(scan, 1, (size_t)len + 2, f) != (size_t)len + 2 || fclose(f)) {
+                fprintf(stderr, "cannot write %s\n", argv[1]);
+                return 1;
+            }
+        }
+        printf("jpeg: %zu header bytes + %llu scan bytes (capacity %zu, bound %zu) + EOI%s%s\n", head_len, (unsigned long long)len,
+               capacity, max_scan, argc > 1 ? " -> " : "", argc > 1 ? argv[1] : "");
+        free(scan);
+        if (hhsr_jpeg_dct(d_norm, H, W, 1, 1, 0, d_coef, coef_bytes, NULL) == 0) return 1; /* quality 0: refused */
+        hipFree(d_coef); hipFree(d_scratch); hipFree(d_scan); hipFree(d_len);
+    }
     /* argument errors come back as codes + messages, never as exceptions */
     if (hhsr_gauss_decimate(d_norm, H, W, W, d_lvl, w2, 3, taps, NT, NULL) == 0) return 1;
     printf("rejected factor 3: %s\n", hhsr_last_error());

@@ -81,6 +81,10 @@ _SIGS = {
     "hhsr_noise_curves_fill": [I32P, I, DP, DP, DP, DP],
     "hhsr_encode_image": [P, I, I, I, I, P, I, SZ, P],
     "hhsr_encode_mask": [P, I, I, I, P, I, I, SZ, P],
+    "hhsr_jpeg_header": [I, I, I, I, I, U8P, SZ, SZP],
+    "hhsr_jpeg_workspace": [I, I, I, I, SZP, SZP, SZP],
+    "hhsr_jpeg_dct": [P, I, I, I, I, I, P, SZ, P],
+    "hhsr_jpeg_entropy": [P, I, I, I, I, P, SZ, P, SZ, P, P],
     "hhsr_clock_probe": [P, L, P],
     "hhsr_merge_burst_chain": [PP, PP, PP, PP, I, I, I, I, I, I, I, P, P, U8P, D, I, I, P, P, P, I, I, P, I, P],
 }

@@ -667,14 +667,29 @@ def process(burst_path, config):
     half to even, M = 255 / 65535: skimage's img_as_ubyte and the reference's 16-bit TIFF rule (hhsr_encode_image) — and only
     the integer image is copied; the result is an ndarray of that dtype, [sH, sW, 3] or, with ``mode: grey``, [sH, sW]
     (channel 0).  With ``robustness.save_mask`` as well, ``debug_dict["robustness mask"]`` is the reference's mask image:
-    uint8 [sH, sW], accumulated robustness / number of comparison frames, nearest neighbour (hhsr_encode_mask)."""
+    uint8 [sH, sW], accumulated robustness / number of comparison frames, nearest neighbour (hhsr_encode_mask).
+    ``config.output = {"format": "jpeg", "quality": 90, "restart_mcus": ...}`` (``format`` absent or "raw": everything above,
+    unchanged): the result is instead the complete baseline JPEG file of the uint8 image as a 1-D uint8 ndarray, coded on
+    the GPU (utils_image.encode_jpeg; one component with ``mode: grey``; write it with utils_image.save_jpeg).  ``dtype``
+    may be absent or "uint8" then, anything else is a ValueError; the robustness mask stays the uint8 array it is."""
     import os
 
     from .utils_dng import infer_width, load_dng_burst, normalize_burst, normalize_packed
 
-    out_dtype = str((config.get("output", None) or {}).get("dtype", "float32"))  # optional section, not in the reference schema
+    out_cfg = config.get("output", None) or {}  # optional section, not in the reference schema
+    out_format = str(out_cfg.get("format", "raw"))
+    if out_format not in ("raw", "jpeg"):
+        raise ValueError(f"config.output.format {out_format!r}: raw or jpeg")
+    out_dtype = str(out_cfg.get("dtype", "uint8" if out_format == "jpeg" else "float32"))
     if out_dtype not in ("float32", "uint8", "uint16"):
         raise ValueError(f"config.output.dtype {out_dtype!r}: float32, uint8 or uint16")
+    if out_format == "jpeg" and out_dtype != "uint8":
+        raise ValueError(f"config.output.format jpeg holds 8-bit samples: output.dtype {out_dtype!r} contradicts it")
+    if out_format == "jpeg":  # (refused now, not after the burst has been merged)
+        if not 1 <= int(out_cfg.get("quality", 90)) <= 100:
+            raise ValueError(f"config.output.quality {out_cfg.get('quality')!r}: 1 .. 100")
+        if out_cfg.get("restart_mcus", None) is not None and not 1 <= int(out_cfg.get("restart_mcus")) <= 65535:
+            raise ValueError(f"config.output.restart_mcus {out_cfg.get('restart_mcus')!r}: 1 .. 65535")
     if isinstance(burst_path, (str, os.PathLike)) and str(burst_path).endswith(".npz"):
         burst = dict(np.load(burst_path))
     elif isinstance(burst_path, (str, os.PathLike)):
@@ -765,10 +780,17 @@ def process(burst_path, config):
     else:  # integer output: encoded on the device, 3 or 6 instead of 12 bytes per pixel cross the host link
         from .utils_image import encode_image, robustness_mask
 
-        output_image = encode_image(out, out_dtype, channels=1 if config.mode == "grey" else None).cpu().numpy()
+        channels = 1 if config.mode == "grey" else None
+        if out_format == "jpeg":  # the whole file's bytes, coded on the device: a tenth of the uint8 samples cross the link
+            from .utils_image import encode_jpeg
+
+            output_image = encode_jpeg(out, quality=out_cfg.get("quality", 90), restart_mcus=out_cfg.get("restart_mcus", None),
+                                       channels=channels)
+        else:
+            output_image = encode_image(out, out_dtype, channels=channels).cpu().numpy()
         if acc_oriented is not None and config.robustness.save_mask:  # the reference's `.rob.png` (run_handheld.py:153-159)
             debug_dict["robustness mask"] = robustness_mask(acc_oriented, max(1, len(raw_comp)),  # (no comparison frame: the map is 0)
-                                                            output_image.shape[:2]).cpu().numpy()
+                                                            tuple(out.shape[:2])).cpu().numpy()
     if acc_oriented is not None:
         debug_dict["accumulated robustness"] = acc_oriented.cpu().numpy()
     return output_image, debug_dict

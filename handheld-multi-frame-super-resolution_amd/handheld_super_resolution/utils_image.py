@@ -320,6 +320,89 @@ def save_png(arr, path):
         f.write(chunk(b"IEND", b""))
 
 
+# ---- JPEG output (include/hhsr.h "JPEG output"; the reference's imsave is cv2.imwrite on the host) ------------------------
+JPEG_RESTART_MCUS = 64  # default restart interval, chosen by measurement (profiles/jpeg_encode.txt)
+
+
+def jpeg_header(H, W, components, quality, restart_mcus):
+    """The bytes in front of the scan (hhsr_jpeg_header: SOI .. SOS) as a uint8 ndarray."""
+    import ctypes as C
+
+    buf = (C.c_uint8 * 1024)()
+    n = C.c_size_t(0)
+    _lib.call("hhsr_jpeg_header", int(H), int(W), int(components), int(quality), int(restart_mcus), buf, 1024, C.byref(n))
+    return np.frombuffer(buf, np.uint8, n.value).copy()
+
+
+def jpeg_workspace(H, W, components, restart_mcus):
+    """(bytes of the coefficients, bytes of the scratch, largest possible scan) of hhsr_jpeg_workspace."""
+    import ctypes as C
+
+    a, b, c = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+    _lib.call("hhsr_jpeg_workspace", int(H), int(W), int(components), int(restart_mcus), C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
+def encode_jpeg(img, quality=90, restart_mcus=None, channels=None, capacity=None):
+    """Device float32 [H, W, 3] or [H, W] -> the complete baseline JPEG file as a 1-D uint8 ndarray (hhsr_jpeg_dct,
+    hhsr_jpeg_entropy): the samples of encode_image(img, "uint8"), 4:4:4, the standard tables at `quality` (IJG scaling),
+    restart intervals of `restart_mcus` MCUs (default JPEG_RESTART_MCUS).  `channels=1` of an [H, W, 3] image: channel 0
+    alone as a grey file (`mode: grey`).  Only the length word and the file's bytes cross the host link: the scan is coded
+    into `capacity` device bytes (default 2 H W C; noise at quality 100 was measured at 1.4 bytes per sample), the length
+    word is read, exactly that many bytes are copied; a scan that did not fit is coded once more into a buffer of the
+    reported length."""
+    if not (torch.is_tensor(img) and img.is_cuda):
+        raise RuntimeError("encode_jpeg expects a tensor on the GPU (the HIP path has no CPU fallback)")
+    src = _lib.f32c(img)
+    if src.dim() not in (2, 3) or (src.dim() == 3 and src.shape[2] not in (1, 3)):
+        raise ValueError(f"encode_jpeg expects [H, W] or [H, W, 3], got {tuple(src.shape)}")
+    H, W = src.shape[:2]
+    ch = 1 if src.dim() == 2 else src.shape[2]
+    och = ch if channels is None else int(channels)
+    if och not in (ch, 1):
+        raise ValueError(f"channels={channels}: {ch} (all of them) or 1 (channel 0)")
+    quality = int(quality)
+    ri = JPEG_RESTART_MCUS if restart_mcus is None else int(restart_mcus)
+    if not 1 <= quality <= 100:
+        raise ValueError(f"quality={quality}: 1 .. 100")
+    if not 1 <= ri <= 65535:
+        raise ValueError(f"restart_mcus={ri}: 1 .. 65535")
+    if not (1 <= H <= 65535 and 1 <= W <= 65535):
+        raise ValueError(f"a JPEG holds at most 65535 x 65535 pixels, got {H} x {W}")
+    head = jpeg_header(H, W, och, quality, ri)
+    coef_bytes, scratch_bytes, _ = jpeg_workspace(H, W, och, ri)
+    dev, stream = src.device, _lib.stream(src.device)
+    coef = torch.empty(coef_bytes // 2, dtype=torch.int16, device=dev)
+    scratch = torch.empty((scratch_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    length = torch.empty(1, dtype=torch.int64, device=dev)
+    _lib.call("hhsr_jpeg_dct", _lib.ptr(src), H, W, ch, och, quality, _lib.ptr(coef), coef_bytes, stream)
+    cap = 2 * H * W * och if capacity is None else int(capacity)
+    for _ in range(2):  # at most one retry, with the length the first pass reported
+        scan = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+        _lib.call("hhsr_jpeg_entropy", _lib.ptr(coef), H, W, och, ri, _lib.ptr(scratch), scratch.numel() * 8,
+                  _lib.ptr(scan), cap, _lib.ptr(length), stream)
+        n = int(length.item())  # (synchronises: the one 8-byte read)
+        if n <= cap:
+            break
+        cap = n
+    else:
+        raise RuntimeError(f"encode_jpeg: the scan needs {n} bytes after a retry with the reported length")
+    out = np.empty(head.size + n + 2, np.uint8)
+    out[:head.size] = head
+    out[head.size:head.size + n] = scan[:n].cpu().numpy()
+    out[-2:] = (0xFF, 0xD9)  # EOI
+    return out
+
+
+def save_jpeg(file_bytes, path):
+    """The array encode_jpeg (or process() with output.format = jpeg) returned -> a file."""
+    a = np.asarray(file_bytes)
+    if a.dtype != np.uint8 or a.ndim != 1 or a.size < 4 or a[0] != 0xFF or a[1] != 0xD8:
+        raise ValueError("save_jpeg expects the 1-D uint8 array of encode_jpeg")
+    with open(path, "wb") as f:
+        f.write(a.tobytes())
+
+
 def _frame_count_denoise(image, r_acc, config, kind, strength, scale, half_index, mode=None):
     # `mode: grey` (monochrome sensors): the reference indexes the accumulated robustness with int(round(y / scale))
     # (utils_image.py:203-204, 260-261) instead of the Bayer branch's half-resolution index.  Upstream reads `mode` (and

@@ -611,6 +611,69 @@ int hhsr_encode_image(const float* image, int H, int W, int channels, int out_ch
 int hhsr_encode_mask(const float* acc_r, int ah, int aw, int n_comp, uint8_t* out, int mH, int mW, size_t out_row_bytes,
                      void* stream);
 
+/* ---- JPEG output (run_handheld.py: imsave = cv2.imwrite writes a JPEG for a `.jpg` path, on the host) --------------------
+ * The finished image as a baseline sequential JPEG (ITU-T T.81, JFIF 1.02 container, 8 bits), encoded on the device: the
+ * entropy-coded scan is left in device memory with its length in a device word, and 5 - 15 times fewer bytes than the
+ * uint8 samples cross the host link.  The file is  header || scan[0 .. length) || FF D9.  tests/jpeg_ref.py is the NumPy /
+ * Python form of everything below.
+ *
+ *   samples   the 8-bit rule of "integer output": NaN -> 0, clip to [0, 1], ONE float32 multiply by 255, rint half to even.
+ *             The JPEG of an image is the JPEG of its uint8 encoding.  channels 1 or 3; out_channels == channels, or 1:
+ *             channel 0 alone as a one-component (grey) file, the `mode: grey` result.
+ *   colour    three components: JFIF full-range YCbCr with the T.871 coefficients, level shift included,
+ *               Y = 0.299 R + 0.587 G + 0.114 B - 128,  Cb = -0.168736 R - 0.331264 G + 0.5 B,
+ *               Cr = 0.5 R - 0.418688 G - 0.081312 B   (float32; nothing is rounded before the transform);
+ *             one component: q - 128.
+ *   sampling  4:4:4 only: an MCU is one 8 x 8 block of each component, in the order Y, Cb, Cr.
+ *   edges     H or W that is no multiple of 8: the last column and the last row of samples are replicated into the padding.
+ *   DCT       the 8 x 8 DCT-II of T.81 A.3.3 in float32 (here: separable, each 8-point pass split into its even and odd
+ *             half); coefficient = rint(c / Q[k]) clamped to the baseline range, DC to [-1024, 1023], AC to [-1023, 1023].
+ *   Q         T.81 K.1 (luma) and K.2 (chroma) scaled by the IJG rule for quality 1 .. 100: s = 5000 / quality (integer
+ *             division) below 50, else 200 - 2 quality; Q = clamp((base s + 50) / 100, 1, 255) (integer division).
+ *   Huffman   T.81 K.3 - K.6 as they stand; no optimisation pass.
+ *   scan      ONE scan, MCUs interleaved, in raster order.  restart_mcus = Ri, 1 .. 65535: a DRI segment in the header and
+ *             RSTm (m = 0, 1, .. 7, 0, ..) after every Ri MCUs except after the last; the DC prediction is 0 at the start of
+ *             each interval; an interval's last byte is padded with 1-bits; every 0xFF byte of entropy-coded data, padding
+ *             bytes included, is followed by 0x00.  Ri >= the number of MCUs: no DRI, no marker.
+ *   limits    H, W <= 65535.
+ *
+ * Coefficients: int16 [n_mcu][out_channels][64], n_mcu = ceil(H / 8) ceil(W / 8) MCUs in raster order, a block's 64 values
+ * in zig-zag order, the DC values raw (not differenced).
+ *
+ * hhsr_jpeg_header (host only, no HIP call): SOI, APP0 (JFIF 1.02, no units, 1 : 1, no thumbnail), one DQT segment per table,
+ *   SOF0 (components 1, 2, 3, each 1 x 1), one DHT segment per table (DC luma, AC luma, then DC chroma, AC chroma with three
+ *   components), DRI when restart_mcus < n_mcu, SOS — into out (HOST, out_capacity bytes); *length = the header's bytes (328 /
+ *   334 for one component, 623 / 629 for three, without / with DRI), set also when out_capacity is too small (error -1 then).
+ * hhsr_jpeg_workspace (host only): *coef_bytes = 128 n_mcu out_channels; *scratch_bytes = the bytes hhsr_jpeg_entropy needs
+ *   (20 per restart interval, rounded up: offsets, sizes and the partial sums of their scan);
+ *   *max_scan_bytes = 432 n_mcu out_channels + 2 (n_intervals - 1): no symbol is longer than a 16-bit code plus 11 magnitude
+ *   bits (the longest code of K.3 - K.6 is 16 bits; a DC difference has at most 11 extra bits, an AC value 10), one symbol
+ *   per coefficient at most (ZRL and EOB stand for coefficients that get none), so a block is at most 64 x 27 bits = 216
+ *   bytes, an interval's padding completes a byte that is already counted, every byte may be 0xFF and then is doubled, and
+ *   every interval but the last is followed by a 2-byte marker.
+ * hhsr_jpeg_dct: image DEVICE float32, compact [H][W][channels], 4-byte aligned -> coef DEVICE int16, 16-byte aligned,
+ *   coef_bytes >= what hhsr_jpeg_workspace reports.  One launch.
+ * hhsr_jpeg_entropy: coef as above -> scan[0 .. capacity) DEVICE bytes (no alignment) and *length (DEVICE uint64, 8-byte
+ *   aligned): the scan's length, ALWAYS written, whatever capacity is.  No byte outside [scan, scan + capacity) is ever
+ *   written, whatever coef holds: every coefficient is clamped to the baseline range as it is read, so that no table index
+ *   leaves its table and no block exceeds the bound above, and every store compares its position with capacity.  If *length >
+ *   capacity the content of scan is unspecified (the caller retries with *length bytes; max_scan_bytes always suffices).
+ *   scratch: DEVICE, 8-byte aligned, scratch_bytes >= what hhsr_jpeg_workspace reports; contents are scratch.  Five launches
+ *   (size pass, three for the exclusive scan of the intervals' sizes, write pass); no atomics on device memory: the bytes
+ *   are a function of the coefficients alone, the same on every run and every stream.
+ * All four: error -1 before any HIP call for a null pointer, H or W <= 0 or > 65535, quality outside 1 .. 100, channels not
+ *   1 or 3, out_channels neither channels nor 1 (where there is no image: not 1 or 3), restart_mcus outside 1 .. 65535, a
+ *   misaligned buffer, buffers that overlap, a buffer smaller than stated.  No allocation, no synchronisation, no copy: every
+ *   launch goes on `stream`, so the calls can be captured into a graph. */
+int hhsr_jpeg_header(int H, int W, int out_channels, int quality, int restart_mcus, uint8_t* out, size_t out_capacity,
+                     size_t* length);
+int hhsr_jpeg_workspace(int H, int W, int out_channels, int restart_mcus, size_t* coef_bytes, size_t* scratch_bytes,
+                        size_t* max_scan_bytes);
+int hhsr_jpeg_dct(const float* image, int H, int W, int channels, int out_channels, int quality, int16_t* coef,
+                  size_t coef_bytes, void* stream);
+int hhsr_jpeg_entropy(const int16_t* coef, int H, int W, int out_channels, int restart_mcus, void* scratch,
+                      size_t scratch_bytes, uint8_t* scan, size_t capacity, uint64_t* length, void* stream);
+
 /* ---- measurement support ------------------------------------------------------------------------------------------
  * Shader-clock probe: one wave that sleeps for `ticks_100mhz` ticks of the constant 100 MHz counter and stores
  * {shader cycles, 100 MHz ticks} at its start and end into out4 (DEVICE uint64[4]); launched on a side stream around a
