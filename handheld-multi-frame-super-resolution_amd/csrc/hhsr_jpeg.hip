@@ -21,164 +21,71 @@
 //              exclusive scan over the intervals' byte counts (three small kernels) gives every interval its offset, so
 //              the write pass stores every byte at its final place and compares every position with the capacity.
 //              No global atomics anywhere: the bytes are a function of the coefficients alone.
+// Extended ("JPEG output, extended"): k_jpeg_dct420 (4:2:0: 16 rows x 256 columns per workgroup, chroma averaged over 2 x 2
+// pixels), k_jpeg_scan<WRITE, true> (any MCU layout, code words from a kernel argument) and k_jpeg_histogram (the scan's
+// symbol counts for hhsr_jpeg_huffman).  The tables, K.2 and the header writer are in hhsr_jpeg_tables.h, free of HIP.
 #include "hhsr_common.h"
+#include "hhsr_jpeg_tables.h"
 
-// ---- tables (T.81 annex K) ------------------------------------------------------------------------------------------------
-namespace {
-#define JPEG_ZIGZAG                                                                                                    \
-    {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,                          \
-     41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,                          \
-     30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63}
-#define JPEG_K1_LUMA                                                                                                   \
-    {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,  69,  56,       \
-     14, 17, 22, 29, 51,  87,  80,  62,  18, 22, 37, 56, 68,  109, 103, 77,  24, 35, 55, 64, 81,  104, 113, 92,       \
-     49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99}
-#define JPEG_K2_CHROMA                                                                                                 \
-    {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99, \
-     99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}
-// (one text each for the host's header writer and the kernels: a host array cannot be indexed by a lane)
-constexpr uint8_t ZIGZAG[64] = JPEG_ZIGZAG;  // ZIGZAG[k]: row-major index u * 8 + v of the k-th coefficient
-constexpr uint8_t K1_LUMA[64] = JPEG_K1_LUMA;
-constexpr uint8_t K2_CHROMA[64] = JPEG_K2_CHROMA;
+// ---- tables, geometry, header writer: hhsr_jpeg_tables.h (no HIP in it) -------------------------------------------------
+using jpeg::HuffCodes;
+using jpeg::HuffSpec;
+using jpeg::HUFF_WORDS;
+using jpeg::SCAN_GROUP;
 
-struct HuffSpec {
-    uint8_t bits[16];   // BITS: codes of length 1 .. 16
-    int n;              // number of symbols
-    uint8_t vals[162];  // HUFFVAL
-};
-constexpr HuffSpec DC_LUMA = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, 12, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11}};
-constexpr HuffSpec DC_CHROMA = {{0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}, 12, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11}};
-constexpr HuffSpec AC_LUMA = {
-    {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d},
-    162,
-    {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71,
-     0x14, 0x32, 0x81, 0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72,
-     0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37,
-     0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59,
-     0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83,
-     0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3,
-     0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
-     0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2,
-     0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa}};
-constexpr HuffSpec AC_CHROMA = {
-    {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77},
-    162,
-    {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22,
-     0x32, 0x81, 0x08, 0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1,
-     0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36,
-     0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58,
-     0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a,
-     0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a,
-     0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
-     0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda,
-     0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa}};
-
-// The device's code tables, made from the four specifications at compile time (annex C): entry = code | length << 16, a
-// symbol the table does not have = 0.  [0] luma, [1] chroma; DC symbols are the 12 categories, AC symbols run << 4 | size.
-struct HuffCodes {
-    uint32_t dc[2][16];
-    uint32_t ac[2][256];
-};
-constexpr void huff_fill(const HuffSpec& s, uint32_t* out) {
-    uint32_t code = 0;
-    int k = 0;
-    for (int len = 1; len <= 16; ++len) {
-        for (int i = 0; i < s.bits[len - 1]; ++i) out[s.vals[k++]] = code++ | ((uint32_t)len << 16);
-        code <<= 1;
-    }
-}
-constexpr HuffCodes huff_codes() {
-    HuffCodes h = {};
-    huff_fill(DC_LUMA, h.dc[0]);
-    huff_fill(DC_CHROMA, h.dc[1]);
-    huff_fill(AC_LUMA, h.ac[0]);
-    huff_fill(AC_CHROMA, h.ac[1]);
-    return h;
-}
-constexpr int HUFF_WORDS = sizeof(HuffCodes) / 4;  // 544
-}  // namespace
-
-__device__ const HuffCodes d_huff = huff_codes();
+__device__ const HuffCodes d_huff = jpeg::huff_codes(jpeg::STANDARD_SPECS);
 __device__ const uint8_t d_zigzag[64] = JPEG_ZIGZAG;
 __device__ const uint8_t d_base_q[2][64] = {JPEG_K1_LUMA, JPEG_K2_CHROMA};
 
-// IJG quality scaling: the percentage s, then a table entry
-static inline int jpeg_scale(int quality) { return quality < 50 ? 5000 / quality : 200 - 2 * quality; }
-__host__ __device__ static inline int jpeg_q(int base, int scale) {
-    const int q = (base * scale + 50) / 100;
-    return q < 1 ? 1 : (q > 255 ? 255 : q);
-}
-
-// ---- geometry shared by the four entry points ----------------------------------------------------------------------------
-constexpr int JPEG_MAX_DIM = 65535;
-constexpr int SCAN_GROUP = 2048;          // intervals per workgroup of the offset scan
-constexpr size_t BLOCK_MAX_BYTES = 216;   // 64 coefficients x (16-bit code + 11 magnitude bits) / 8
-struct JpegGeom {
-    int mcux, mcuy;
-    size_t n_mcu, n_int, n_groups;
-    size_t coef_bytes, scratch_bytes, max_scan;
-};
-static inline JpegGeom jpeg_geom(int H, int W, int comps, int restart_mcus) {
-    JpegGeom g;
-    g.mcux = (W + 7) / 8;
-    g.mcuy = (H + 7) / 8;
-    g.n_mcu = (size_t)g.mcux * g.mcuy;  // <= 8192^2
-    g.n_int = (g.n_mcu + restart_mcus - 1) / restart_mcus;
-    g.n_groups = (g.n_int + SCAN_GROUP - 1) / SCAN_GROUP;
-    g.coef_bytes = g.n_mcu * comps * 64 * sizeof(int16_t);
-    // scratch: uint64 offsets[n_int] | uint64 group totals[n_groups] | uint32 sizes[n_int]
-    g.scratch_bytes = (g.n_int + g.n_groups) * sizeof(uint64_t) + g.n_int * sizeof(uint32_t);
-    g.max_scan = 2 * BLOCK_MAX_BYTES * g.n_mcu * comps + 2 * (g.n_int - 1);
-    return g;
-}
 #define JPEG_ARG_DIMS() \
-    HHSR_ARG(H > 0 && W > 0 && H <= JPEG_MAX_DIM && W <= JPEG_MAX_DIM)
+    HHSR_ARG(H > 0 && W > 0 && H <= jpeg::MAX_DIM && W <= jpeg::MAX_DIM)
 
-// ---- header (host only) -----------------------------------------------------------------------------------------------------
-extern "C" int hhsr_jpeg_header(int H, int W, int out_channels, int quality, int restart_mcus, uint8_t* out,
-                                size_t out_capacity, size_t* length) {
+static inline bool jpeg_disjoint(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 + na <= b0 || b0 + nb <= a0;
+}
+
+#define JPEG_ARG_SUB() \
+    HHSR_ARG((subsampling == 0 || subsampling == 1) && (subsampling == 0 || out_channels == 3))
+
+// ---- header, workspace, table construction (host only) ------------------------------------------------------------------------
+extern "C" int hhsr_jpeg_header_ex(int H, int W, int out_channels, int quality, int restart_mcus, int subsampling,
+                                   const uint8_t* spec, uint8_t* out, size_t out_capacity, size_t* length) {
     HHSR_ARG(out != nullptr && length != nullptr);
     JPEG_ARG_DIMS();
     HHSR_ARG(out_channels == 1 || out_channels == 3);
     HHSR_ARG(quality >= 1 && quality <= 100);
     HHSR_ARG(restart_mcus >= 1 && restart_mcus <= 65535);
-    const int nc = out_channels;
-    const JpegGeom g = jpeg_geom(H, W, nc, restart_mcus);
-    const bool dri = (size_t)restart_mcus < g.n_mcu;
-    const HuffSpec* specs[4] = {&DC_LUMA, &AC_LUMA, &DC_CHROMA, &AC_CHROMA};
-    const int ntab = nc == 1 ? 1 : 2;
-    size_t need = 2 + 18 + (size_t)ntab * 69 + (10 + 3 * nc) + (dri ? 6 : 0) + (8 + 2 * nc);
-    for (int t = 0; t < 2 * ntab; ++t) need += 21 + specs[t]->n;
-    *length = need;
-    HHSR_ARG(out_capacity >= need);
-    uint8_t* p = out;
-    auto u8 = [&](int v) { *p++ = (uint8_t)v; };
-    auto u16 = [&](int v) { *p++ = (uint8_t)(v >> 8); *p++ = (uint8_t)v; };
-    u16(0xFFD8);
-    u16(0xFFE0); u16(16);  // APP0: JFIF 1.02, no units, aspect 1:1, no thumbnail
-    for (const char c : {'J', 'F', 'I', 'F', '\0'}) u8(c);
-    u8(1); u8(2); u8(0); u16(1); u16(1); u8(0); u8(0);
-    const int scale = jpeg_scale(quality);
-    for (int t = 0; t < ntab; ++t) {
-        u16(0xFFDB); u16(67); u8(t);
-        for (int k = 0; k < 64; ++k) u8(jpeg_q((t ? K2_CHROMA : K1_LUMA)[ZIGZAG[k]], scale));
-    }
-    u16(0xFFC0); u16(8 + 3 * nc); u8(8); u16(H); u16(W); u8(nc);
-    for (int c = 0; c < nc; ++c) { u8(c + 1); u8(0x11); u8(c ? 1 : 0); }
-    for (int t = 0; t < 2 * ntab; ++t) {
-        const HuffSpec& s = *specs[t];
-        u16(0xFFC4); u16(19 + s.n); u8(((t & 1) << 4) | (t >> 1));
-        for (int i = 0; i < 16; ++i) u8(s.bits[i]);
-        for (int i = 0; i < s.n; ++i) u8(s.vals[i]);
-    }
-    if (dri) { u16(0xFFDD); u16(4); u16(restart_mcus); }
-    u16(0xFFDA); u16(6 + 2 * nc); u8(nc);
-    for (int c = 0; c < nc; ++c) { u8(c + 1); u8(c ? 0x11 : 0x00); }
-    u8(0); u8(63); u8(0);
-    if ((size_t)(p - out) != need) {
+    JPEG_ARG_SUB();
+    HuffSpec store[4];
+    const HuffSpec* specs[4];
+    const bool spec_is_valid = jpeg::specs_from_abi(spec, out_channels == 1 ? 2 : 4, store, specs);
+    HHSR_ARG(spec_is_valid);
+    const int rc = jpeg::write_header(H, W, out_channels, quality, restart_mcus, subsampling, specs, out, out_capacity, length);
+    HHSR_ARG(rc != 1 /* out_capacity >= *length */);
+    if (rc != 0) {
         hhsr_set_error("hhsr_jpeg_header: internal length mismatch");
         return -2;
     }
+    return 0;
+}
+
+extern "C" int hhsr_jpeg_header(int H, int W, int out_channels, int quality, int restart_mcus, uint8_t* out,
+                                size_t out_capacity, size_t* length) {
+    return hhsr_jpeg_header_ex(H, W, out_channels, quality, restart_mcus, 0, nullptr, out, out_capacity, length);
+}
+
+extern "C" int hhsr_jpeg_workspace_ex(int H, int W, int out_channels, int restart_mcus, int subsampling, size_t* coef_bytes,
+                                      size_t* scratch_bytes, size_t* max_scan_bytes) {
+    HHSR_ARG(coef_bytes != nullptr && scratch_bytes != nullptr && max_scan_bytes != nullptr);
+    JPEG_ARG_DIMS();
+    HHSR_ARG(out_channels == 1 || out_channels == 3);
+    HHSR_ARG(restart_mcus >= 1 && restart_mcus <= 65535);
+    JPEG_ARG_SUB();
+    const jpeg::Geom g = jpeg::geom(H, W, out_channels, restart_mcus, subsampling);
+    *coef_bytes = g.coef_bytes;
+    *scratch_bytes = g.scratch_bytes > g.hist_bytes ? g.scratch_bytes : g.hist_bytes;  // entropy coder | histogram
+    *max_scan_bytes = g.max_scan;
     return 0;
 }
 
@@ -188,10 +95,25 @@ extern "C" int hhsr_jpeg_workspace(int H, int W, int out_channels, int restart_m
     JPEG_ARG_DIMS();
     HHSR_ARG(out_channels == 1 || out_channels == 3);
     HHSR_ARG(restart_mcus >= 1 && restart_mcus <= 65535);
-    const JpegGeom g = jpeg_geom(H, W, out_channels, restart_mcus);
+    const jpeg::Geom g = jpeg::geom(H, W, out_channels, restart_mcus);
     *coef_bytes = g.coef_bytes;
     *scratch_bytes = g.scratch_bytes;
     *max_scan_bytes = g.max_scan;
+    return 0;
+}
+
+extern "C" int hhsr_jpeg_huffman(const uint64_t* counts, int n_tables, uint8_t* spec) {
+    HHSR_ARG(counts != nullptr && spec != nullptr);
+    HHSR_ARG(n_tables == 2 || n_tables == 4);
+    HHSR_ARG(((uintptr_t)counts & 7) == 0);
+    HHSR_ARG(jpeg_disjoint(counts, (size_t)n_tables * 256 * sizeof(uint64_t), spec, (size_t)n_tables * jpeg::SPEC_BYTES));
+    uint8_t built[4][jpeg::SPEC_BYTES];
+    for (int t = 0; t < n_tables; ++t) {
+        const bool counts_are_usable = jpeg::huffman_build(counts + (size_t)t * 256, built[t]);
+        HHSR_ARG(counts_are_usable /* a table's counts: not all zero, their sum below 2^64 */);
+    }
+    for (int t = 0; t < n_tables; ++t)
+        for (int k = 0; k < jpeg::SPEC_BYTES; ++k) spec[(size_t)t * jpeg::SPEC_BYTES + k] = built[t][k];
     return 0;
 }
 
@@ -220,6 +142,30 @@ __device__ __forceinline__ void dct8(float* x) {
     x[7] = 0.5f * (c7 * d0 - c5 * d1 + c3 * d2 - c1 * d3);
 }
 
+// A block's row pass, in place: 8 consecutive floats as two b128
+__device__ __forceinline__ void dct_row_pass(float* row) {
+    float4 a = reinterpret_cast<float4*>(row)[0], b = reinterpret_cast<float4*>(row)[1];
+    float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    dct8(x);
+    reinterpret_cast<float4*>(row)[0] = make_float4(x[0], x[1], x[2], x[3]);
+    reinterpret_cast<float4*>(row)[1] = make_float4(x[4], x[5], x[6], x[7]);
+}
+
+// Column v of a block (8 floats `pitch` apart), then the division by q (row-major) into o at the zig-zag positions
+__device__ __forceinline__ void dct_col_pass(const float* col, int pitch, int v, const float* q, const uint8_t* zpos,
+                                             int16_t* o) {
+    float x[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) x[u] = col[u * pitch];
+    dct8(x);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const int k = u * 8 + v;
+        const float lo = k == 0 ? -1024.f : -1023.f;
+        o[zpos[k]] = (int16_t)fminf(fmaxf(rintf(x[u] / q[k]), lo), 1023.f);
+    }
+}
+
 constexpr int DCT_MCUS = 32;                   // MCUs (= blocks of a component) per workgroup: 256 columns
 constexpr int DCT_PITCH = DCT_MCUS * 8 + 4;    // floats per LDS row: 16-byte aligned rows
 
@@ -233,7 +179,7 @@ __global__ void __launch_bounds__(256) k_jpeg_dct(const float* __restrict__ imag
     __shared__ uint8_t zpos[64];              // row-major index -> zig-zag position
     const int t = threadIdx.x, bx0 = blockIdx.x * DCT_MCUS, by = blockIdx.y;
     if (t < 64) zpos[d_zigzag[t]] = (uint8_t)t;
-    if (t < 64 * (NC == 1 ? 1 : 2)) Q[t >> 6][t & 63] = (float)jpeg_q(d_base_q[t >> 6][t & 63], scale);
+    if (t < 64 * (NC == 1 ? 1 : 2)) Q[t >> 6][t & 63] = (float)jpeg::q_entry(d_base_q[t >> 6][t & 63], scale);
     {
         const int xs = min(bx0 * 8 + t, W - 1);  // replication of the last column
 #pragma unroll
@@ -252,30 +198,13 @@ __global__ void __launch_bounds__(256) k_jpeg_dct(const float* __restrict__ imag
     }
     __syncthreads();
 #pragma unroll
-    for (int i = t; i < NC * 256; i += 256) {  // row passes: (component, row, block)
-        float* row = &P[i >> 8][(i >> 5) & 7][(i & 31) * 8];
-        float4 a = reinterpret_cast<float4*>(row)[0], b = reinterpret_cast<float4*>(row)[1];
-        float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-        dct8(x);
-        reinterpret_cast<float4*>(row)[0] = make_float4(x[0], x[1], x[2], x[3]);
-        reinterpret_cast<float4*>(row)[1] = make_float4(x[4], x[5], x[6], x[7]);
-    }
+    for (int i = t; i < NC * 256; i += 256)  // row passes: (component, row, block)
+        dct_row_pass(&P[i >> 8][(i >> 5) & 7][(i & 31) * 8]);
     __syncthreads();
 #pragma unroll
     for (int i = t; i < NC * 256; i += 256) {  // column passes: (component, block, column), then the division
-        const int c = i >> 8, col = i & 255, b = col >> 3, v = col & 7;
-        float x[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) x[u] = P[c][u][col];
-        dct8(x);
-        int16_t* o = &O[(b * NC + c) * 64];
-        const float* q = Q[c ? 1 : 0];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int k = u * 8 + v;
-            const float lo = k == 0 ? -1024.f : -1023.f;
-            o[zpos[k]] = (int16_t)fminf(fmaxf(rintf(x[u] / q[k]), lo), 1023.f);
-        }
+        const int c = i >> 8, col = i & 255, b = col >> 3;
+        dct_col_pass(&P[c][0][col], DCT_PITCH, col & 7, Q[c ? 1 : 0], zpos, &O[(b * NC + c) * 64]);
     }
     __syncthreads();
     const int nvalid = min(DCT_MCUS, mcux - bx0);  // MCUs of this workgroup that exist
@@ -283,31 +212,98 @@ __global__ void __launch_bounds__(256) k_jpeg_dct(const float* __restrict__ imag
     for (int i = t; i < nvalid * NC * 8; i += 256) dst[i] = reinterpret_cast<const uint4*>(O)[i];
 }
 
-static inline bool jpeg_disjoint(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 + na <= b0 || b0 + nb <= a0;
+// 4:2:0: a workgroup takes 16 image rows x 256 columns = 16 MCUs.  Thread t loads column t of the 16 rows; Y goes to LDS
+// as 2 x 32 blocks with the arithmetic of k_jpeg_dct; Cb and Cr stay unrounded float32, and a chroma sample is
+// 0.25 ((c00 + c01) + (c10 + c11)): the horizontal sums come from the neighbouring lane (c + its neighbour is the same sum in
+// both lanes of a pair), the even lane adds the two rows' sums.  96 blocks, 768 row and 768 column passes: three of each per
+// thread, as RGB 4:4:4.  O holds the 16 MCUs in coding order: Y(0,0) Y(0,1) Y(1,0) Y(1,1) Cb Cr.
+constexpr int DCT420_MCUS = 16;
+constexpr int DCT420_CPITCH = DCT420_MCUS * 8 + 4;
+
+__global__ void __launch_bounds__(256) k_jpeg_dct420(const float* __restrict__ image, int H, int W, int mcux, int scale,
+                                                      int16_t* __restrict__ coef) {
+    __shared__ __attribute__((aligned(16))) float Y[16][DCT_PITCH];
+    __shared__ __attribute__((aligned(16))) float C[2][8][DCT420_CPITCH];
+    __shared__ __attribute__((aligned(16))) int16_t O[DCT420_MCUS * 6 * 64];
+    __shared__ float Q[2][64];
+    __shared__ uint8_t zpos[64];
+    const int t = threadIdx.x, bx0 = blockIdx.x * DCT420_MCUS, by = blockIdx.y;
+    if (t < 64) zpos[d_zigzag[t]] = (uint8_t)t;
+    if (t < 128) Q[t >> 6][t & 63] = (float)jpeg::q_entry(d_base_q[t >> 6][t & 63], scale);
+    {
+        const int xs = min(bx0 * 16 + t, W - 1);  // replication of the last column
+#pragma unroll
+        for (int r2 = 0; r2 < 8; ++r2) {
+            float hb[2], hr[2];  // cb, cr: this column + its neighbour, rows 2 r2 and 2 r2 + 1
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int r = 2 * r2 + k;
+                const int ys = min(by * 16 + r, H - 1);  // ... and of the last row
+                const float* __restrict__ p = image + ((size_t)ys * W + xs) * 3;
+                const float R = jpeg_sample(p[0]), G = jpeg_sample(p[1]), B = jpeg_sample(p[2]);
+                Y[r][t] = 0.299f * R + 0.587f * G + 0.114f * B - 128.f;
+                const float cb = -0.168736f * R - 0.331264f * G + 0.5f * B;
+                const float cr = 0.5f * R - 0.418688f * G - 0.081312f * B;
+                const float nb = __shfl_xor(cb, 1, 64), nr = __shfl_xor(cr, 1, 64);
+                hb[k] = cb + nb;  // (the pair's sum in both of its lanes: float addition commutes)
+                hr[k] = cr + nr;
+            }
+            if ((t & 1) == 0) {
+                C[0][r2][t >> 1] = 0.25f * (hb[0] + hb[1]);
+                C[1][r2][t >> 1] = 0.25f * (hr[0] + hr[1]);
+            }
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = t; i < 768; i += 256) {  // row passes: Y (row, block) x 512, then (component, row, block) x 256
+        if (i < 512) dct_row_pass(&Y[i >> 5][(i & 31) * 8]);
+        else dct_row_pass(&C[(i >> 7) & 1][(i >> 4) & 7][(i & 15) * 8]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = t; i < 768; i += 256) {  // column passes
+        if (i < 512) {                    // Y: (block row, column); block b of the row is Y(row, b & 1) of MCU b >> 1
+            const int br = i >> 8, col = i & 255, b = col >> 3;
+            dct_col_pass(&Y[br * 8][col], DCT_PITCH, col & 7, Q[0], zpos, &O[((b >> 1) * 6 + br * 2 + (b & 1)) * 64]);
+        } else {                          // Cb, Cr: (component, column); block b is MCU b's
+            const int c = (i >> 7) & 1, col = i & 127;
+            dct_col_pass(&C[c][0][col], DCT420_CPITCH, col & 7, Q[1], zpos, &O[((col >> 3) * 6 + 4 + c) * 64]);
+        }
+    }
+    __syncthreads();
+    const int nvalid = min(DCT420_MCUS, mcux - bx0);  // MCUs of this workgroup that exist
+    uint4* __restrict__ dst = reinterpret_cast<uint4*>(coef + ((size_t)by * mcux + bx0) * (6 * 64));
+    for (int i = t; i < nvalid * 6 * 8; i += 256) dst[i] = reinterpret_cast<const uint4*>(O)[i];
 }
 
-extern "C" int hhsr_jpeg_dct(const float* image, int H, int W, int channels, int out_channels, int quality, int16_t* coef,
-                             size_t coef_bytes, void* stream) {
+extern "C" int hhsr_jpeg_dct_ex(const float* image, int H, int W, int channels, int out_channels, int quality,
+                                int subsampling, int16_t* coef, size_t coef_bytes, void* stream) {
     HHSR_ARG(image != nullptr && coef != nullptr);
     JPEG_ARG_DIMS();
     HHSR_ARG(channels == 1 || channels == 3);
     HHSR_ARG(out_channels == channels || out_channels == 1);
     HHSR_ARG(quality >= 1 && quality <= 100);
+    JPEG_ARG_SUB();
     HHSR_ARG(((uintptr_t)image & 3) == 0 && ((uintptr_t)coef & 15) == 0);
-    const JpegGeom g = jpeg_geom(H, W, out_channels, 1);
+    const jpeg::Geom g = jpeg::geom(H, W, out_channels, 1, subsampling);
     HHSR_ARG(coef_bytes >= g.coef_bytes);
     HHSR_ARG(jpeg_disjoint(image, (size_t)H * W * channels * sizeof(float), coef, g.coef_bytes));
-    const dim3 grid((unsigned)hhsr_cdiv(g.mcux, DCT_MCUS), (unsigned)g.mcuy), block(256);
-    const int scale = jpeg_scale(quality);
-#define HHSR_JPEG_DCT(NC, STEP) \
-    hipLaunchKernelGGL((k_jpeg_dct<NC, STEP>), grid, block, 0, (hipStream_t)stream, image, H, W, g.mcux, scale, coef)
-    if (out_channels == 3) HHSR_JPEG_DCT(3, 3);
-    else if (channels == 3) HHSR_JPEG_DCT(1, 3);
-    else HHSR_JPEG_DCT(1, 1);
+    const dim3 grid((unsigned)hhsr_cdiv(g.mcux, subsampling ? DCT420_MCUS : DCT_MCUS), (unsigned)g.mcuy), block(256);
+    const int scale = jpeg::q_scale(quality);
+#define HHSR_JPEG_DCT(KERNEL) \
+    hipLaunchKernelGGL(KERNEL, grid, block, 0, (hipStream_t)stream, image, H, W, g.mcux, scale, coef)
+    if (subsampling) HHSR_JPEG_DCT(k_jpeg_dct420);
+    else if (out_channels == 3) HHSR_JPEG_DCT((k_jpeg_dct<3, 3>));
+    else if (channels == 3) HHSR_JPEG_DCT((k_jpeg_dct<1, 3>));
+    else HHSR_JPEG_DCT((k_jpeg_dct<1, 1>));
 #undef HHSR_JPEG_DCT
     HHSR_LAUNCHED();
+}
+
+extern "C" int hhsr_jpeg_dct(const float* image, int H, int W, int channels, int out_channels, int quality, int16_t* coef,
+                             size_t coef_bytes, void* stream) {
+    return hhsr_jpeg_dct_ex(image, H, W, channels, out_channels, quality, 0, coef, coef_bytes, stream);
 }
 
 // ---- entropy coding -----------------------------------------------------------------------------------------------------------
@@ -316,10 +312,10 @@ constexpr int SCAN_WORDS = 3328;
 
 __device__ __forceinline__ int jpeg_clamp_coef(int v, bool dc) { return max(dc ? -1024 : -1023, min(v, 1023)); }
 
-// A block's bit string, symbol by symbol, through put(bits, count): count <= 26, bits < 2^count.
-template <typename Put>
-__device__ __forceinline__ void jpeg_code_block(const int16_t* __restrict__ blk, int pred, const uint32_t* __restrict__ dc,
-                                                const uint32_t* __restrict__ ac, Put put) {
+// A block's symbols in coding order through sym(is_ac, symbol, value, size): the DC difference (symbol = its category), then
+// per non-zero AC value ZRL (0xF0) for every 16 zeros before it and run << 4 | size, and EOB (0x00) if the block ends in zeros.
+template <typename Sym>
+__device__ __forceinline__ void jpeg_walk_block(const int16_t* __restrict__ blk, int pred, Sym sym) {
     int run = 0;
 #pragma unroll 1
     for (int g = 0; g < 8; ++g) {
@@ -329,43 +325,72 @@ __device__ __forceinline__ void jpeg_code_block(const int16_t* __restrict__ blk,
         for (int j = 0; j < 8; ++j) {
             const int raw = (int)(int16_t)(ws[j >> 1] >> ((j & 1) * 16));
             if (g == 0 && j == 0) {
-                const int d = jpeg_clamp_coef(raw, true) - pred;       // |d| <= 2047: category <= 11
+                const int d = jpeg_clamp_coef(raw, true) - pred;       // |d| <= 2047: category <= 11 < 16
                 const int cat = 32 - __clz(abs(d));
-                const uint32_t e = dc[cat];                             // cat <= 11 < 16
-                put((e & 0xffffu) << cat | (uint32_t)((d < 0 ? d - 1 : d) & ((1 << cat) - 1)), (int)(e >> 16) + cat);
+                sym(false, cat, d, cat);
             } else {
                 const int v = jpeg_clamp_coef(raw, false);             // |v| <= 1023: size <= 10
                 if (v == 0) {
                     ++run;
                 } else {
                     while (run >= 16) {
-                        const uint32_t z = ac[0xF0];
-                        put(z & 0xffffu, (int)(z >> 16));
+                        sym(true, 0xF0, 0, 0);
                         run -= 16;
                     }
                     const int cat = 32 - __clz(abs(v));
-                    const uint32_t e = ac[(run << 4) | cat];            // run <= 15, cat <= 10: < 256
-                    put((e & 0xffffu) << cat | (uint32_t)((v < 0 ? v - 1 : v) & ((1 << cat) - 1)), (int)(e >> 16) + cat);
+                    sym(true, (run << 4) | cat, v, cat);                // run <= 15, cat <= 10: < 256
                     run = 0;
                 }
             }
         }
     }
-    if (run) put(ac[0] & 0xffffu, (int)(ac[0] >> 16));  // EOB
+    if (run) sym(true, 0, 0, 0);
+}
+
+// A block's bit string, symbol by symbol, through put(bits, count): count <= 26, bits < 2^count.  Returns whether the
+// block needed a symbol the tables do not have (entry 0: nothing but the magnitude bits is put for it).
+template <typename Put>
+__device__ __forceinline__ bool jpeg_code_block(const int16_t* __restrict__ blk, int pred, const uint32_t* __restrict__ dc,
+                                                const uint32_t* __restrict__ ac, Put put) {
+    bool missing = false;
+    jpeg_walk_block(blk, pred, [&](bool is_ac, int s, int v, int cat) {
+        const uint32_t e = (is_ac ? ac : dc)[s];
+        missing |= e == 0;
+        put((e & 0xffffu) << cat | (uint32_t)((v < 0 ? v - 1 : v) & ((1 << cat) - 1)), (int)(e >> 16) + cat);
+    });
+    return missing;
 }
 
 // One wave per restart interval.  WRITE false: sizes[interval] = its bytes (stuffing, padding and RSTm included).
 // WRITE true: the bytes to scan + offsets[interval], every position compared with capacity.
-template <bool WRITE>
+//
+// EX false: 4:4:4 with K.3 - K.6 (hhsr_jpeg_entropy: `comps` blocks per MCU, component = block index mod comps, the tables of
+// d_huff).  EX true (hhsr_jpeg_entropy_ex): `comps` is the blocks per MCU of `layout`, the code words are the argument
+// `codes`, and a symbol they do not have (entry 0) makes the write pass store UINT64_MAX over the length word.
+template <bool EX>
+struct ScanTables {};  // (EX false: nothing travels with the launch)
+template <>
+struct ScanTables<true> {
+    uint32_t chroma;   // bit p: position p of an MCU codes with the chroma tables
+    uint32_t dist;     // 4 bits per position: the DC prediction is the block that many blocks back
+    uint64_t* length;  // the length word
+    HuffCodes codes;   // 544 words, by value: no copy to enqueue, the call stays capturable
+};
+template <bool WRITE, bool EX>
 __global__ void __launch_bounds__(64) k_jpeg_scan(const int16_t* __restrict__ coef, int comps, unsigned restart_mcus,
                                                    size_t n_mcu, size_t n_int, uint32_t* __restrict__ sizes,
                                                    const uint64_t* __restrict__ offsets, uint8_t* __restrict__ scan,
-                                                   size_t capacity) {
+                                                   size_t capacity, ScanTables<EX> ex) {
     __shared__ uint32_t huff[HUFF_WORDS];
     __shared__ uint32_t bits[SCAN_WORDS];
     const int lane = threadIdx.x;
     const size_t it = blockIdx.x;
-    for (int i = lane; i < HUFF_WORDS; i += 64) huff[i] = reinterpret_cast<const uint32_t*>(&d_huff)[i];
+    if constexpr (EX) {
+        for (int i = lane; i < HUFF_WORDS; i += 64) huff[i] = reinterpret_cast<const uint32_t*>(&ex.codes)[i];
+    } else {
+        for (int i = lane; i < HUFF_WORDS; i += 64) huff[i] = reinterpret_cast<const uint32_t*>(&d_huff)[i];
+    }
+    bool missing = false;  // (EX) a symbol without a code
     for (int i = lane; i < SCAN_WORDS; i += 64) bits[i] = 0;
     const uint32_t* dc_tab = huff;             // [2][16]
     const uint32_t* ac_tab = huff + 32;        // [2][256]
@@ -379,12 +404,20 @@ __global__ void __launch_bounds__(64) k_jpeg_scan(const int16_t* __restrict__ co
     for (unsigned b0 = 0; b0 < nblk; b0 += 64) {
         const unsigned j = b0 + lane;
         const bool live = j < nblk;
-        const int c = live ? (int)(j % comps) : 0, tab = c ? 1 : 0;
+        const int c = live ? (int)(j % comps) : 0;
+        int tab = c ? 1 : 0, back = comps;
+        if constexpr (EX) {
+            tab = (int)(ex.chroma >> c & 1);
+            back = (int)(ex.dist >> (4 * c) & 15);
+        }
         const int16_t* __restrict__ blk = base + (size_t)(live ? j : 0) * 64;
-        // DC prediction: the same component of the previous MCU of this interval
-        const int pred = (live && j >= (unsigned)comps) ? jpeg_clamp_coef(blk[-comps * 64], true) : 0;
+        // DC prediction: the block of the same component before this one in the interval (4:4:4: in the previous MCU)
+        const int pred = (live && j >= (unsigned)back) ? jpeg_clamp_coef(blk[-back * 64], true) : 0;
         int len = 0;
-        if (live) jpeg_code_block(blk, pred, dc_tab + tab * 16, ac_tab + tab * 256, [&](uint32_t, int n) { len += n; });
+        if (live) {
+            const bool bad = jpeg_code_block(blk, pred, dc_tab + tab * 16, ac_tab + tab * 256, [&](uint32_t, int n) { len += n; });
+            if (EX && WRITE) missing |= bad;
+        }
         int incl = len;  // inclusive wave prefix sum
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
@@ -445,6 +478,9 @@ __global__ void __launch_bounds__(64) k_jpeg_scan(const int16_t* __restrict__ co
         if (marker && lane == 0) {
             if (pos < capacity) scan[pos] = 0xff;
             if (pos + 1 < capacity) scan[pos + 1] = (uint8_t)(0xd0 + (it & 7));
+        }
+        if constexpr (EX) {  // (every interval that finds one stores the same word, behind the scan of the sizes)
+            if (__any(missing) && lane == 0) *ex.length = UINT64_MAX;
         }
     } else if (lane == 0) {
         sizes[it] = (uint32_t)(pos + (marker ? 2 : 0));  // <= 2 x 216 x 196605 + 2
@@ -517,6 +553,56 @@ __global__ void __launch_bounds__(256) k_jpeg_offsets(const uint32_t* __restrict
     }
 }
 
+// The five launches of the entropy coder.  EX false: hhsr_jpeg_entropy's kernels, untouched by the extended route.
+template <bool EX>
+static void jpeg_entropy_launch(const int16_t* coef, const jpeg::Geom& g, int restart_mcus, void* scratch, uint8_t* scan,
+                                size_t capacity, uint64_t* length, const ScanTables<EX>& ex, hipStream_t s) {
+    uint64_t* offsets = (uint64_t*)scratch;
+    uint64_t* totals = offsets + g.n_int;
+    uint32_t* sizes = (uint32_t*)(totals + g.n_groups);
+    const dim3 wave(64), wg(256), ints((unsigned)g.n_int), groups((unsigned)g.n_groups);  // n_int <= 2^26
+    hipLaunchKernelGGL((k_jpeg_scan<false, EX>), ints, wave, 0, s, coef, g.bpm, (unsigned)restart_mcus, g.n_mcu, g.n_int,
+                       sizes, (const uint64_t*)nullptr, (uint8_t*)nullptr, (size_t)0, ex);
+    hipLaunchKernelGGL(k_jpeg_group_totals, groups, wg, 0, s, (const uint32_t*)sizes, g.n_int, totals);
+    hipLaunchKernelGGL(k_jpeg_scan_groups, dim3(1), wg, 0, s, totals, g.n_groups, length);
+    hipLaunchKernelGGL(k_jpeg_offsets, groups, wg, 0, s, (const uint32_t*)sizes, g.n_int, (const uint64_t*)totals, offsets);
+    hipLaunchKernelGGL((k_jpeg_scan<true, EX>), ints, wave, 0, s, coef, g.bpm, (unsigned)restart_mcus, g.n_mcu, g.n_int,
+                       sizes, (const uint64_t*)offsets, scan, capacity, ex);
+}
+
+// position -> tables and prediction distance of an MCU's blocks: Y Cb Cr (or Y alone) | Y Y Y Y Cb Cr
+static inline void jpeg_layout(const jpeg::Geom& g, int subsampling, uint32_t* chroma, uint32_t* dist) {
+    *chroma = subsampling ? 0x30u : 0x6u & ((1u << g.bpm) - 1);
+    *dist = subsampling ? 0x661113u : (uint32_t)g.bpm * 0x111u;
+}
+
+extern "C" int hhsr_jpeg_entropy_ex(const int16_t* coef, int H, int W, int out_channels, int restart_mcus, int subsampling,
+                                    const uint8_t* spec, void* scratch, size_t scratch_bytes, uint8_t* scan, size_t capacity,
+                                    uint64_t* length, void* stream) {
+    HHSR_ARG(coef != nullptr && scratch != nullptr && scan != nullptr && length != nullptr);
+    JPEG_ARG_DIMS();
+    HHSR_ARG(out_channels == 1 || out_channels == 3);
+    HHSR_ARG(restart_mcus >= 1 && restart_mcus <= 65535);
+    JPEG_ARG_SUB();
+    HHSR_ARG(((uintptr_t)coef & 15) == 0 && ((uintptr_t)scratch & 7) == 0 && ((uintptr_t)length & 7) == 0);
+    const jpeg::Geom g = jpeg::geom(H, W, out_channels, restart_mcus, subsampling);
+    HHSR_ARG(scratch_bytes >= g.scratch_bytes);
+    HHSR_ARG(capacity <= SIZE_MAX - (uintptr_t)scan);
+    HHSR_ARG(jpeg_disjoint(coef, g.coef_bytes, scratch, g.scratch_bytes) && jpeg_disjoint(coef, g.coef_bytes, scan, capacity) &&
+             jpeg_disjoint(coef, g.coef_bytes, length, 8) && jpeg_disjoint(scratch, g.scratch_bytes, scan, capacity) &&
+             jpeg_disjoint(scratch, g.scratch_bytes, length, 8) && jpeg_disjoint(scan, capacity, length, 8));
+    HuffSpec store[4];
+    const HuffSpec* specs[4];
+    const bool spec_is_valid = jpeg::specs_from_abi(spec, out_channels == 1 ? 2 : 4, store, specs);
+    HHSR_ARG(spec_is_valid);
+    ScanTables<true> ex;
+    jpeg_layout(g, subsampling, &ex.chroma, &ex.dist);
+    ex.length = length;
+    ex.codes = jpeg::huff_codes(specs);  // annex C, on the host
+    jpeg_entropy_launch<true>(coef, g, restart_mcus, scratch, scan, capacity, length, ex, (hipStream_t)stream);
+    HHSR_LAUNCHED();
+}
+
 extern "C" int hhsr_jpeg_entropy(const int16_t* coef, int H, int W, int out_channels, int restart_mcus, void* scratch,
                                  size_t scratch_bytes, uint8_t* scan, size_t capacity, uint64_t* length, void* stream) {
     HHSR_ARG(coef != nullptr && scratch != nullptr && scan != nullptr && length != nullptr);
@@ -524,23 +610,77 @@ extern "C" int hhsr_jpeg_entropy(const int16_t* coef, int H, int W, int out_chan
     HHSR_ARG(out_channels == 1 || out_channels == 3);
     HHSR_ARG(restart_mcus >= 1 && restart_mcus <= 65535);
     HHSR_ARG(((uintptr_t)coef & 15) == 0 && ((uintptr_t)scratch & 7) == 0 && ((uintptr_t)length & 7) == 0);
-    const JpegGeom g = jpeg_geom(H, W, out_channels, restart_mcus);
+    const jpeg::Geom g = jpeg::geom(H, W, out_channels, restart_mcus);
     HHSR_ARG(scratch_bytes >= g.scratch_bytes);
     HHSR_ARG(capacity <= SIZE_MAX - (uintptr_t)scan);
     HHSR_ARG(jpeg_disjoint(coef, g.coef_bytes, scratch, g.scratch_bytes) && jpeg_disjoint(coef, g.coef_bytes, scan, capacity) &&
              jpeg_disjoint(coef, g.coef_bytes, length, 8) && jpeg_disjoint(scratch, g.scratch_bytes, scan, capacity) &&
              jpeg_disjoint(scratch, g.scratch_bytes, length, 8) && jpeg_disjoint(scan, capacity, length, 8));
-    uint64_t* offsets = (uint64_t*)scratch;
-    uint64_t* totals = offsets + g.n_int;
-    uint32_t* sizes = (uint32_t*)(totals + g.n_groups);
+    jpeg_entropy_launch<false>(coef, g, restart_mcus, scratch, scan, capacity, length, ScanTables<false>(), (hipStream_t)stream);
+    HHSR_LAUNCHED();
+}
+
+// ---- symbol counts --------------------------------------------------------------------------------------------------------------
+// A block's symbols need its own coefficients and one DC value before it, nothing of the interval's other blocks: a thread
+// per block, a bounded number of persistent workgroups that stride over all blocks, counts in LDS [4][256] (DC luma, AC luma,
+// DC chroma, AC chroma; a workgroup sees fewer than 2^32 symbols: at most 2^28 blocks over 512 workgroups), one partial
+// table per workgroup, summed by a second launch.  Integer sums: the same counts whatever the order.
+__global__ void __launch_bounds__(jpeg::HIST_THREADS) k_jpeg_histogram(const int16_t* __restrict__ coef, unsigned bpm,
+                                                                        uint32_t chroma, uint32_t dist, unsigned restart_mcus,
+                                                                        size_t n_blocks, uint64_t* __restrict__ partial) {
+    __shared__ uint32_t cnt[4 * 256];
+    const int t = threadIdx.x;
+    for (int i = t; i < 4 * 256; i += jpeg::HIST_THREADS) cnt[i] = 0;
+    __syncthreads();
+    for (size_t b = (size_t)blockIdx.x * jpeg::HIST_THREADS + t; b < n_blocks; b += (size_t)gridDim.x * jpeg::HIST_THREADS) {
+        const size_t mcu = b / bpm;
+        const unsigned p = (unsigned)(b - mcu * bpm);
+        const unsigned j = (unsigned)(mcu % restart_mcus) * bpm + p;  // the block's index in its interval
+        const unsigned back = dist >> (4 * p) & 15;
+        const int16_t* __restrict__ blk = coef + b * 64;
+        const int pred = j >= back ? jpeg_clamp_coef(blk[-(int)back * 64], true) : 0;
+        uint32_t* tab = cnt + (chroma >> p & 1) * 512;
+        jpeg_walk_block(blk, pred, [&](bool is_ac, int s, int, int) { atomicAdd(&tab[(is_ac ? 256 : 0) + s], 1u); });
+    }
+    __syncthreads();
+    for (int i = t; i < 4 * 256; i += jpeg::HIST_THREADS) partial[(size_t)blockIdx.x * 1024 + i] = cnt[i];
+}
+
+// 64 workgroups of 16 bins: 16 lanes read the bins of one partial table (128 consecutive bytes), the 16 groups of lanes
+// take every 16th table, LDS adds the groups up.  (One thread per bin walking all tables alone is a chain of n_partial
+// dependent-latency loads: measured 0.2 ms of the 0.27 ms of both launches at 48 MP.)
+__global__ void __launch_bounds__(256) k_jpeg_histogram_sum(const uint64_t* __restrict__ partial, unsigned n_partial,
+                                                             uint64_t* __restrict__ counts) {
+    __shared__ uint64_t part[16][16];
+    const unsigned bin = threadIdx.x & 15, slice = threadIdx.x >> 4;
+    uint64_t sum = 0;
+    for (unsigned g = slice; g < n_partial; g += 16) sum += partial[(size_t)g * 1024 + blockIdx.x * 16 + bin];
+    part[slice][bin] = sum;
+    __syncthreads();
+    if (slice == 0) {
+#pragma unroll
+        for (int k = 1; k < 16; ++k) sum += part[k][bin];
+        counts[blockIdx.x * 16 + bin] = sum;
+    }
+}
+
+extern "C" int hhsr_jpeg_histogram(const int16_t* coef, int H, int W, int out_channels, int subsampling, int restart_mcus,
+                                   uint64_t* counts, void* scratch, size_t scratch_bytes, void* stream) {
+    HHSR_ARG(coef != nullptr && counts != nullptr && scratch != nullptr);
+    JPEG_ARG_DIMS();
+    HHSR_ARG(out_channels == 1 || out_channels == 3);
+    HHSR_ARG(restart_mcus >= 1 && restart_mcus <= 65535);
+    JPEG_ARG_SUB();
+    HHSR_ARG(((uintptr_t)coef & 15) == 0 && ((uintptr_t)scratch & 7) == 0 && ((uintptr_t)counts & 7) == 0);
+    const jpeg::Geom g = jpeg::geom(H, W, out_channels, restart_mcus, subsampling);
+    HHSR_ARG(scratch_bytes >= g.hist_bytes);
+    HHSR_ARG(jpeg_disjoint(coef, g.coef_bytes, scratch, g.hist_bytes) && jpeg_disjoint(coef, g.coef_bytes, counts, jpeg::HIST_TABLE_BYTES) &&
+             jpeg_disjoint(scratch, g.hist_bytes, counts, jpeg::HIST_TABLE_BYTES));
+    uint32_t chroma, dist;
+    jpeg_layout(g, subsampling, &chroma, &dist);
     hipStream_t s = (hipStream_t)stream;
-    const dim3 wave(64), wg(256), ints((unsigned)g.n_int), groups((unsigned)g.n_groups);  // n_int <= 2^26
-    hipLaunchKernelGGL(k_jpeg_scan<false>, ints, wave, 0, s, coef, out_channels, (unsigned)restart_mcus, g.n_mcu, g.n_int,
-                       sizes, (const uint64_t*)nullptr, (uint8_t*)nullptr, (size_t)0);
-    hipLaunchKernelGGL(k_jpeg_group_totals, groups, wg, 0, s, (const uint32_t*)sizes, g.n_int, totals);
-    hipLaunchKernelGGL(k_jpeg_scan_groups, dim3(1), wg, 0, s, totals, g.n_groups, length);
-    hipLaunchKernelGGL(k_jpeg_offsets, groups, wg, 0, s, (const uint32_t*)sizes, g.n_int, (const uint64_t*)totals, offsets);
-    hipLaunchKernelGGL(k_jpeg_scan<true>, ints, wave, 0, s, coef, out_channels, (unsigned)restart_mcus, g.n_mcu, g.n_int,
-                       sizes, (const uint64_t*)offsets, scan, capacity);
+    hipLaunchKernelGGL(k_jpeg_histogram, dim3((unsigned)g.hist_groups), dim3(jpeg::HIST_THREADS), 0, s, coef, (unsigned)g.bpm,
+                       chroma, dist, (unsigned)restart_mcus, g.n_blocks, (uint64_t*)scratch);
+    hipLaunchKernelGGL(k_jpeg_histogram_sum, dim3(64), dim3(256), 0, s, (const uint64_t*)scratch, (unsigned)g.hist_groups, counts);
     HHSR_LAUNCHED();
 }

@@ -85,6 +85,12 @@ _SIGS = {
     "hhsr_jpeg_workspace": [I, I, I, I, SZP, SZP, SZP],
     "hhsr_jpeg_dct": [P, I, I, I, I, I, P, SZ, P],
     "hhsr_jpeg_entropy": [P, I, I, I, I, P, SZ, P, SZ, P, P],
+    "hhsr_jpeg_header_ex": [I, I, I, I, I, I, U8P, U8P, SZ, SZP],
+    "hhsr_jpeg_workspace_ex": [I, I, I, I, I, SZP, SZP, SZP],
+    "hhsr_jpeg_dct_ex": [P, I, I, I, I, I, I, P, SZ, P],
+    "hhsr_jpeg_histogram": [P, I, I, I, I, I, P, P, SZ, P],
+    "hhsr_jpeg_huffman": [C.POINTER(C.c_uint64), I, U8P],
+    "hhsr_jpeg_entropy_ex": [P, I, I, I, I, I, U8P, P, SZ, P, SZ, P, P],
     "hhsr_clock_probe": [P, L, P],
     "hhsr_merge_burst_chain": [PP, PP, PP, PP, I, I, I, I, I, I, I, P, P, U8P, D, I, I, P, P, P, I, I, P, I, P],
 }

@@ -671,7 +671,11 @@ def process(burst_path, config):
     ``config.output = {"format": "jpeg", "quality": 90, "restart_mcus": ...}`` (``format`` absent or "raw": everything above,
     unchanged): the result is instead the complete baseline JPEG file of the uint8 image as a 1-D uint8 ndarray, coded on
     the GPU (utils_image.encode_jpeg; one component with ``mode: grey``; write it with utils_image.save_jpeg).  ``dtype``
-    may be absent or "uint8" then, anything else is a ValueError; the robustness mask stays the uint8 array it is."""
+    may be absent or "uint8" then, anything else is a ValueError; the robustness mask stays the uint8 array it is.
+    With ``format: jpeg``, ``subsampling: 444 | 420`` (string or integer; 420 halves the chroma planes and is refused with
+    ``mode: grey``) and ``huffman: standard | optimized`` (tables made for the image: a smaller file for one more
+    synchronisation) choose the encoder's options; both keys are read only then, anything else is a ValueError before the
+    burst is merged."""
     import os
 
     from .utils_dng import infer_width, load_dng_burst, normalize_burst, normalize_packed
@@ -690,6 +694,12 @@ def process(burst_path, config):
             raise ValueError(f"config.output.quality {out_cfg.get('quality')!r}: 1 .. 100")
         if out_cfg.get("restart_mcus", None) is not None and not 1 <= int(out_cfg.get("restart_mcus")) <= 65535:
             raise ValueError(f"config.output.restart_mcus {out_cfg.get('restart_mcus')!r}: 1 .. 65535")
+        from .utils_image import jpeg_option
+
+        out_sub = jpeg_option("subsampling", out_cfg.get("subsampling", "444"))
+        out_huffman = jpeg_option("huffman", out_cfg.get("huffman", "standard"))
+        if out_sub == "420" and config.mode == "grey":
+            raise ValueError("config.output.subsampling 420 needs three components: mode grey writes one")
     if isinstance(burst_path, (str, os.PathLike)) and str(burst_path).endswith(".npz"):
         burst = dict(np.load(burst_path))
     elif isinstance(burst_path, (str, os.PathLike)):
@@ -785,7 +795,7 @@ def process(burst_path, config):
             from .utils_image import encode_jpeg
 
             output_image = encode_jpeg(out, quality=out_cfg.get("quality", 90), restart_mcus=out_cfg.get("restart_mcus", None),
-                                       channels=channels)
+                                       channels=channels, subsampling=out_sub, huffman=out_huffman)
         else:
             output_image = encode_image(out, out_dtype, channels=channels).cpu().numpy()
         if acc_oriented is not None and config.robustness.save_mask:  # the reference's `.rob.png` (run_handheld.py:153-159)

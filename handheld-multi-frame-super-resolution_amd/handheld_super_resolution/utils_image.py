@@ -321,7 +321,8 @@ def save_png(arr, path):
 
 
 # ---- JPEG output (include/hhsr.h "JPEG output"; the reference's imsave is cv2.imwrite on the host) ------------------------
-JPEG_RESTART_MCUS = 64  # default restart interval, chosen by measurement (profiles/jpeg_encode.txt)
+JPEG_RESTART_MCUS = 64  # default restart interval, chosen by measurement (profiles/jpeg_encode.txt); the sweep for 4:2:0,
+#                         whose MCUs are 16 x 16 pixels, keeps it (profiles/jpeg_subsampling.txt)
 
 
 def jpeg_header(H, W, components, quality, restart_mcus):
@@ -343,14 +344,81 @@ def jpeg_workspace(H, W, components, restart_mcus):
     return a.value, b.value, c.value
 
 
-def encode_jpeg(img, quality=90, restart_mcus=None, channels=None, capacity=None):
+JPEG_SUBSAMPLINGS = {"444": 0, "420": 1}  # the `subsampling` argument of the hhsr_jpeg_*_ex entry points
+JPEG_HUFFMAN = ("standard", "optimized")
+
+
+def jpeg_option(name, value):
+    """The canonical string of an encode_jpeg / config.output option: subsampling "444" | "420" (the integers too: YAML
+    parses them as such), huffman "standard" | "optimized".  Anything else is a ValueError."""
+    allowed = JPEG_SUBSAMPLINGS if name == "subsampling" else JPEG_HUFFMAN
+    text = str(value) if isinstance(value, (str, int)) and not isinstance(value, bool) else None
+    if text not in allowed:
+        raise ValueError(f"{name}={value!r}: one of {', '.join(allowed)}")
+    return text
+
+
+def _jpeg_spec(spec, tables):
+    """A table specification ([tables, 272] uint8, or None for K.3 - K.6) as the C ABI's argument."""
+    import ctypes as C
+
+    if spec is None:
+        return None
+    a = np.ascontiguousarray(spec, np.uint8)
+    if a.shape != (tables, 272):
+        raise ValueError(f"a Huffman specification of {tables} tables is uint8 [{tables}, 272], got {a.shape}")
+    return a.ctypes.data_as(C.POINTER(C.c_uint8))
+
+
+def jpeg_header_ex(H, W, components, quality, restart_mcus, subsampling=0, spec=None):
+    """hhsr_jpeg_header_ex: jpeg_header for `subsampling` (0: 4:4:4, 1: 4:2:0) with the tables of `spec`."""
+    import ctypes as C
+
+    buf = (C.c_uint8 * 2048)()
+    n = C.c_size_t(0)
+    _lib.call("hhsr_jpeg_header_ex", int(H), int(W), int(components), int(quality), int(restart_mcus), int(subsampling),
+              _jpeg_spec(spec, 2 if int(components) == 1 else 4), buf, 2048, C.byref(n))
+    return np.frombuffer(buf, np.uint8, n.value).copy()
+
+
+def jpeg_workspace_ex(H, W, components, restart_mcus, subsampling=0):
+    """(bytes of the coefficients, bytes of the scratch, largest possible scan) of hhsr_jpeg_workspace_ex."""
+    import ctypes as C
+
+    a, b, c = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+    _lib.call("hhsr_jpeg_workspace_ex", int(H), int(W), int(components), int(restart_mcus), int(subsampling), C.byref(a),
+              C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
+def jpeg_huffman(counts):
+    """hhsr_jpeg_huffman: symbol counts [2 or 4, 256] (host) -> the optimal table specification, uint8 [2 or 4, 272]."""
+    import ctypes as C
+
+    c = np.ascontiguousarray(counts, np.uint64)
+    if c.ndim != 2 or c.shape[1] != 256:
+        raise ValueError(f"jpeg_huffman expects counts [2 or 4, 256], got {c.shape}")
+    spec = np.zeros((c.shape[0], 272), np.uint8)
+    _lib.call("hhsr_jpeg_huffman", c.ctypes.data_as(C.POINTER(C.c_uint64)), int(c.shape[0]),
+              spec.ctypes.data_as(C.POINTER(C.c_uint8)))
+    return spec
+
+
+def encode_jpeg(img, quality=90, restart_mcus=None, channels=None, capacity=None, subsampling="444", huffman="standard"):
     """Device float32 [H, W, 3] or [H, W] -> the complete baseline JPEG file as a 1-D uint8 ndarray (hhsr_jpeg_dct,
     hhsr_jpeg_entropy): the samples of encode_image(img, "uint8"), 4:4:4, the standard tables at `quality` (IJG scaling),
     restart intervals of `restart_mcus` MCUs (default JPEG_RESTART_MCUS).  `channels=1` of an [H, W, 3] image: channel 0
     alone as a grey file (`mode: grey`).  Only the length word and the file's bytes cross the host link: the scan is coded
     into `capacity` device bytes (default 2 H W C; noise at quality 100 was measured at 1.4 bytes per sample), the length
     word is read, exactly that many bytes are copied; a scan that did not fit is coded once more into a buffer of the
-    reported length."""
+    reported length.
+
+    `subsampling="420"` (three components only): Cb and Cr at half resolution in both directions, MCUs of 16 x 16 pixels,
+    which `restart_mcus` then counts.  `huffman="optimized"`: the tables are made for this image — hhsr_jpeg_histogram
+    counts the scan's symbols on the device, the 8 KB of counts are copied to the host, hhsr_jpeg_huffman builds the
+    tables, they go into the header and back to the coder as code words.  That is ONE MORE SYNCHRONISATION than the
+    standard tables need (the copy of the counts, before the scan can be coded).  Either option goes through the
+    hhsr_jpeg_*_ex entry points; with both at their defaults the calls are exactly those of the four original ones."""
     if not (torch.is_tensor(img) and img.is_cuda):
         raise RuntimeError("encode_jpeg expects a tensor on the GPU (the HIP path has no CPU fallback)")
     src = _lib.f32c(img)
@@ -369,19 +437,41 @@ def encode_jpeg(img, quality=90, restart_mcus=None, channels=None, capacity=None
         raise ValueError(f"restart_mcus={ri}: 1 .. 65535")
     if not (1 <= H <= 65535 and 1 <= W <= 65535):
         raise ValueError(f"a JPEG holds at most 65535 x 65535 pixels, got {H} x {W}")
-    head = jpeg_header(H, W, och, quality, ri)
-    coef_bytes, scratch_bytes, _ = jpeg_workspace(H, W, och, ri)
+    sub = JPEG_SUBSAMPLINGS[jpeg_option("subsampling", subsampling)]
+    optimized = jpeg_option("huffman", huffman) == "optimized"
+    if sub and och != 3:
+        raise ValueError("subsampling=420 needs three components")
+    ex = bool(sub or optimized)
     dev, stream = src.device, _lib.stream(src.device)
+    coef_bytes, scratch_bytes, _ = jpeg_workspace_ex(H, W, och, ri, sub) if ex else jpeg_workspace(H, W, och, ri)
     coef = torch.empty(coef_bytes // 2, dtype=torch.int16, device=dev)
     scratch = torch.empty((scratch_bytes + 7) // 8, dtype=torch.int64, device=dev)
     length = torch.empty(1, dtype=torch.int64, device=dev)
-    _lib.call("hhsr_jpeg_dct", _lib.ptr(src), H, W, ch, och, quality, _lib.ptr(coef), coef_bytes, stream)
+    spec = None
+    if not ex:
+        head = jpeg_header(H, W, och, quality, ri)
+        _lib.call("hhsr_jpeg_dct", _lib.ptr(src), H, W, ch, och, quality, _lib.ptr(coef), coef_bytes, stream)
+    else:
+        _lib.call("hhsr_jpeg_dct_ex", _lib.ptr(src), H, W, ch, och, quality, sub, _lib.ptr(coef), coef_bytes, stream)
+        if optimized:
+            counts = torch.empty((4, 256), dtype=torch.int64, device=dev)
+            _lib.call("hhsr_jpeg_histogram", _lib.ptr(coef), H, W, och, sub, ri, _lib.ptr(counts), _lib.ptr(scratch),
+                      scratch.numel() * 8, stream)
+            tables = 2 if och == 1 else 4
+            spec = jpeg_huffman(counts.cpu().numpy().view(np.uint64)[:tables])  # (synchronises: the 8 KB of counts)
+        head = jpeg_header_ex(H, W, och, quality, ri, sub, spec)
     cap = 2 * H * W * och if capacity is None else int(capacity)
     for _ in range(2):  # at most one retry, with the length the first pass reported
         scan = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
-        _lib.call("hhsr_jpeg_entropy", _lib.ptr(coef), H, W, och, ri, _lib.ptr(scratch), scratch.numel() * 8,
-                  _lib.ptr(scan), cap, _lib.ptr(length), stream)
+        if not ex:
+            _lib.call("hhsr_jpeg_entropy", _lib.ptr(coef), H, W, och, ri, _lib.ptr(scratch), scratch.numel() * 8,
+                      _lib.ptr(scan), cap, _lib.ptr(length), stream)
+        else:
+            _lib.call("hhsr_jpeg_entropy_ex", _lib.ptr(coef), H, W, och, ri, sub, _jpeg_spec(spec, 2 if och == 1 else 4),
+                      _lib.ptr(scratch), scratch.numel() * 8, _lib.ptr(scan), cap, _lib.ptr(length), stream)
         n = int(length.item())  # (synchronises: the one 8-byte read)
+        if n < 0:  # UINT64_MAX (cannot happen with tables counted at the same interval)
+            raise RuntimeError("encode_jpeg: the Huffman tables lack a symbol the scan needs")
         if n <= cap:
             break
         cap = n

@@ -674,6 +674,65 @@ int hhsr_jpeg_dct(const float* image, int H, int W, int channels, int out_channe
 int hhsr_jpeg_entropy(const int16_t* coef, int H, int W, int out_channels, int restart_mcus, void* scratch,
                       size_t scratch_bytes, uint8_t* scan, size_t capacity, uint64_t* length, void* stream);
 
+/* JPEG output, extended: 4:2:0 chroma subsampling and Huffman tables made for the image.  The four entry points above keep
+ * their signatures and results; with subsampling 0 and spec NULL an _ex function gives exactly what its namesake gives.
+ * tests/jpeg_ex_ref.py is the NumPy / Python form of everything below.
+ *
+ *   subsampling  0: 4:4:4, as above.  1: 4:2:0, out_channels == 3 only:
+ *     MCU        16 x 16 pixels; mcux = ceil(W / 16), mcuy = ceil(H / 16); the last column and the last row are replicated
+ *                up to the next multiple of 16.
+ *     Y          exactly the Y of 4:4:4: the same float32 operations on the same samples, block for block.
+ *     Cb, Cr     per pixel in float32 as above, unrounded; a chroma sample is 0.25f * ((c00 + c01) + (c10 + c11)) of its
+ *                2 x 2 pixels (c00 c01 the upper row): libjpeg's h2v2 box filter without its integer rounding.  Nothing
+ *                is rounded before the transform.
+ *     blocks     coefficients int16 [n_mcu][6][64] in zig-zag order, in the order of T.81 A.2.3: Y(0,0), Y(0,1), Y(1,0),
+ *                Y(1,1), Cb, Cr (Y(r,c): block row r, block column c of the MCU).  coef_bytes = 768 n_mcu.
+ *     header     SOF0 sampling factors 0x22 for Y, 0x11 for Cb and Cr; the same quantisation tables.
+ *     scan       the restart interval counts 16 x 16 MCUs.  The DC prediction runs per component through the interval in
+ *                coding order: the first Y block of an MCU predicts from the fourth Y block of the MCU before it.
+ *     limits     max_scan_bytes = 432 * 6 n_mcu + 2 (n_intervals - 1).
+ *   spec         a Huffman table specification, HOST uint8_t [n_tables][16 + 256]: BITS (the number of codes of length 1 ..
+ *                16), then HUFFVAL (the symbols, by code), zero-filled.  Row order DC luma, AC luma, DC chroma, AC chroma;
+ *                n_tables = 2 with one component, otherwise 4.  NULL: K.3 - K.6.  A DC symbol is the category of the
+ *                difference (0 .. 11), an AC symbol run << 4 | size, 0xF0 = ZRL, 0x00 = EOB.  A row is refused unless it
+ *                holds 1 .. 256 symbols, none twice, DC symbols <= 11, and BITS is a prefix code by annex C in which no
+ *                code is all 1-bits.
+ *
+ * hhsr_jpeg_header_ex (host only): hhsr_jpeg_header with the sampling factors of `subsampling` and the DHT segments of `spec`.
+ * hhsr_jpeg_workspace_ex (host only): the sizes for `subsampling`; *scratch_bytes covers both hhsr_jpeg_entropy_ex (20 bytes
+ *   per interval, rounded up) and hhsr_jpeg_histogram (8192 bytes per workgroup: one for every 256 blocks, at most 512).
+ * hhsr_jpeg_dct_ex: hhsr_jpeg_dct for `subsampling`.  One launch.
+ * hhsr_jpeg_histogram: coef -> counts, DEVICE uint64 [4][256], 8-byte aligned: counts[t][s] = how often the scan of these
+ *   coefficients at this restart interval emits symbol s of table t (row order as in spec).  The counts depend on
+ *   restart_mcus because the DC prediction restarts with the interval.  The call overwrites counts; with one component rows
+ *   2 and 3 are zero.  Exact integers, the same whatever the order of the launch's workgroups.  scratch: DEVICE, 8-byte
+ *   aligned.  Two launches (counts per workgroup in LDS, then the sum of the workgroups' tables); no atomics on device memory.
+ * hhsr_jpeg_huffman (host only, HOST pointers): counts [n_tables][256] -> spec [n_tables][16 + 256] by T.81 K.2 with
+ *   libjpeg's choices: a reserved symbol 256 of count 1, so that no code is all 1-bits; the two least non-zero counts are
+ *   merged, ties going to the larger symbol index (the first of the two is searched over all symbols, the second over all
+ *   others); lengths above 16 are shortened by Figure K.3; the reserved symbol is removed from the longest length in use;
+ *   HUFFVAL is ordered by the length K.2 found (before the shortening), then by symbol.  Error -1 also for a table whose
+ *   counts are all zero or sum to 2^64 or more; spec is written only when every table was built.
+ * hhsr_jpeg_entropy_ex: hhsr_jpeg_entropy for `subsampling` with the tables of `spec`.  The host turns spec into code words
+ *   (annex C) that travel as a by-value kernel argument of 544 words: no copy, no allocation, the call stays capturable, and
+ *   spec may be freed on return.  If a block needs a symbol the tables do not have — tables built at another restart
+ *   interval, for instance — *length = UINT64_MAX and the content of scan is unspecified; still no byte outside
+ *   [scan, scan + capacity) is written.  Five launches, as hhsr_jpeg_entropy.
+ * All: error -1 before any HIP call for what the four entry points above refuse, subsampling outside 0 .. 1, subsampling 1
+ *   with out_channels != 3, n_tables not 2 or 4, an invalid row of spec. */
+int hhsr_jpeg_header_ex(int H, int W, int out_channels, int quality, int restart_mcus, int subsampling, const uint8_t* spec,
+                        uint8_t* out, size_t out_capacity, size_t* length);
+int hhsr_jpeg_workspace_ex(int H, int W, int out_channels, int restart_mcus, int subsampling, size_t* coef_bytes,
+                           size_t* scratch_bytes, size_t* max_scan_bytes);
+int hhsr_jpeg_dct_ex(const float* image, int H, int W, int channels, int out_channels, int quality, int subsampling,
+                     int16_t* coef, size_t coef_bytes, void* stream);
+int hhsr_jpeg_histogram(const int16_t* coef, int H, int W, int out_channels, int subsampling, int restart_mcus,
+                        uint64_t* counts, void* scratch, size_t scratch_bytes, void* stream);
+int hhsr_jpeg_huffman(const uint64_t* counts, int n_tables, uint8_t* spec);
+int hhsr_jpeg_entropy_ex(const int16_t* coef, int H, int W, int out_channels, int restart_mcus, int subsampling,
+                         const uint8_t* spec, void* scratch, size_t scratch_bytes, uint8_t* scan, size_t capacity,
+                         uint64_t* length, void* stream);
+
 /* ---- measurement support ------------------------------------------------------------------------------------------
  * Shader-clock probe: one wave that sleeps for `ticks_100mhz` ticks of the constant 100 MHz counter and stores
  * {shader cycles, 100 MHz ticks} at its start and end into out4 (DEVICE uint64[4]); launched on a side stream around a
