@@ -280,6 +280,45 @@ def test_post_edges_golden(golden):
         assert_close(post.postprocess(pin, do_gamma=True, **kw), g[f"pp_{h}x{w}_gamma"], 0, 1e-6, f"gamma {h}x{w}")
 
 
+def test_frame_stats_edges_golden(golden):
+    """The per-frame pass at its borders against the reference's own functions (tools/refsim stage "frame_stats_edges"):
+    compute_guide_image + compute_local_stats at the six degenerate shapes and at 34 x 66 for every image family of
+    tests/frame_stats_cases.py, estimate_kernels under both laws wherever the reference can be stepped — 34 x 66 in Bayer
+    and grey mode, 4 x 4 in grey mode.  It cannot be stepped where the gradient grid has a side of 0 or 1 samples (Bayer
+    2 x 2 .. 70 x 2 and 4 x 4, grey 2 x 2 .. 70 x 2): F.conv2d refuses an image smaller than its filter and `.squeeze()`
+    (kernels.py:116) drops a gradient axis of length 1; there the scalar restatement of tests/test_frame_stats_ref.py is
+    the only witness.  Everything the reference computed is reproduced bit for bit, NaN masks included."""
+    import frame_stats_cases as fc
+
+    g = golden("frame_stats_edges")
+    assert sorted(g["cov_ran"]) == ["34x66_bayer", "34x66_grey", "4x4_grey"]
+    t = fc.config().merging.tuning
+    assert np.array_equal(g["tuning"], [t.k_detail, t.k_denoise, t.D_th, t.D_tr, t.k_stretch, t.k_shrink])
+    assert g["cfa"].tolist() == fc.GOLDEN_CFA and g["wb"].tolist() == fc.GOLDEN_WB
+    n_cov = 0
+    for H, W in fc.REF_SHAPES:
+        for fam in fc.STAT_FAMILIES:
+            key = fc.golden_key(fam, H, W)
+            raw = g[key + "_raw"]
+            assert np.array_equal(raw, fc.image(fam, H, W), equal_nan=True), key
+            with np.errstate(all="ignore"):
+                m, v = oracle.local_stats(oracle.guide_image(raw, fc.GOLDEN_CFA, fc.GOLDEN_WB))
+            assert np.array_equal(m, g[key + "_means"], equal_nan=True), key
+            assert np.array_equal(v, g[key + "_vars"], equal_nan=True), key
+            for mode in ("bayer", "grey"):
+                for law in fc.LAWS:
+                    name = f"{key}_{mode}_{law}"
+                    if f"{H}x{W}_{mode}" not in g["cov_ran"] or fam not in fc.COV_FAMILIES:
+                        assert name not in g.files
+                        continue
+                    c = oracle.estimate_kernels(raw, fc.family_config(fam, law, mode))
+                    assert np.array_equal(c[..., 0, 1], c[..., 1, 0], equal_nan=True)
+                    got = np.stack([c[..., 0, 0], c[..., 0, 1], c[..., 1, 1]], -1)
+                    assert np.array_equal(got, g[name], equal_nan=True), name
+                    n_cov += 1
+    assert n_cov == 3 * 2 * len(fc.COV_FAMILIES)
+
+
 def test_post_gauss_and_unsharp_known_answers():
     """Oracle-only parts of the post path: the gauss denoiser (upstream cannot run it) and the unsharp mask (restated
     through scipy.ndimage.gaussian_filter, the routine skimage.filters.unsharp_mask calls)."""

@@ -571,6 +571,68 @@ def stage_post_edges():
     save("post_edges", **out)
 
 
+def _load_frame_stats_cases():
+    import importlib.util
+
+    p = os.path.join(GOLDEN, "..", "frame_stats_cases.py")
+    spec = importlib.util.spec_from_file_location("_refsim_frame_stats_cases", os.path.abspath(p))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
+def stage_frame_stats_edges():
+    """Alg. 5 and Alg. 7-8 at degenerate grids and on the structured images of tests/frame_stats_cases.py (fixture
+    frame_stats_edges.npz): the reference's own compute_guide_image / compute_local_stats at every shape, and its
+    estimate_kernels (both laws, Bayer and grey mode) wherever it can be stepped.  It cannot where the gradient grid has a
+    side of 0 or 1 samples: F.conv2d refuses an image smaller than its filter, and `.squeeze()` (kernels.py:116) drops a
+    gradient axis of length 1, after which the transposes fail.  Which (shape, mode) ran is recorded ("cov_ran") and
+    asserted here.  Covariances are stored as their three distinct entries (xx, xy, yy; yx == xy is asserted)."""
+    k, rb = loader.ref("kernels"), loader.ref("robustness")
+    params = loader.ref("params")
+    fc = _load_frame_stats_cases()
+    cfa, wb = np.array(fc.GOLDEN_CFA), np.array(fc.GOLDEN_WB)
+    d_cfa, d_wb = cuda.to_device(cfa), cuda.to_device(wb)
+    out = {"cfa": cfa, "wb": wb}
+
+    def config(law, mode, beta):
+        cfg = base_config(mode=mode)
+        cfg.merging.tuning.update({"k_detail": "SNR_based", "k_denoise": "SNR_based", "D_th": "SNR_based", "D_tr": "SNR_based"})
+        params.update_snr_config(cfg, fc.SNR)
+        cfg.merging.selection_law = law
+        cfg.noise_model.beta = beta
+        return cfg
+
+    t = config("linear", "bayer", BETA).merging.tuning
+    out["tuning"] = np.array([t.k_detail, t.k_denoise, t.D_th, t.D_tr, t.k_stretch, t.k_shrink], np.float64)
+    ran = []
+    for H, W in fc.REF_SHAPES:
+        for fam in fc.STAT_FAMILIES:
+            key = fc.golden_key(fam, H, W)
+            raw = np.array(fc.image(fam, H, W))
+            out[key + "_raw"] = raw
+            m, v = rb.compute_local_stats(rb.compute_guide_image(cuda.to_device(raw), d_cfa, d_wb))
+            out[key + "_means"], out[key + "_vars"] = npy(m), npy(v)
+            if fam not in fc.COV_FAMILIES:
+                continue
+            for mode in ("bayer", "grey"):
+                for law in fc.LAWS:
+                    try:
+                        c = npy(k.estimate_kernels(cuda.to_device(raw), config(law, mode, fc.beta_of(fam))))
+                    except (RuntimeError, IndexError, ValueError) as e:
+                        gh, gw = (H // 2, W // 2) if mode == "bayer" else (H, W)
+                        assert min(gh, gw) <= 2, (key, mode, e)
+                        continue
+                    assert np.array_equal(c[..., 0, 1], c[..., 1, 0], equal_nan=True)
+                    out[f"{key}_{mode}_{law}"] = np.stack([c[..., 0, 0], c[..., 0, 1], c[..., 1, 1]], -1)
+                    if (H, W, mode) not in ran:
+                        ran.append((H, W, mode))
+    out["cov_ran"] = np.array([f"{h}x{w}_{m}" for h, w, m in ran])
+    print("    estimate_kernels stepped at:", ", ".join(out["cov_ran"]))
+    assert set(out["cov_ran"]) == {"4x4_grey", "34x66_bayer", "34x66_grey"}, out["cov_ran"]
+    save("frame_stats_edges", **out)
+
+
 def stage_grey_mode():
     """`mode: grey` (monochrome sensors): the reference's own estimate_kernels / init_robustness / compute_robustness /
     merge / merge_ref on one-channel frames, and main() end to end (128x128, 3 frames, x2, Ts=16, all-L2)."""
@@ -759,7 +821,7 @@ def stage_frontend():
 STAGES = {
     "frontend": stage_frontend,
     "grey_mode": stage_grey_mode,
-    "post": stage_post, "post_edges": stage_post_edges,
+    "post": stage_post, "post_edges": stage_post_edges, "frame_stats_edges": stage_frame_stats_edges,
     "grey": stage_grey, "downsample": stage_downsample, "hessian": stage_hessian, "bm_l2": stage_bm_l2,
     "ica": stage_ica, "upscale": stage_upscale, "kernels": stage_kernels, "robustness": stage_robustness,
     "merge": stage_merge, "params": stage_params, "e2e": stage_e2e, "e2e_x1": stage_e2e_x1,
