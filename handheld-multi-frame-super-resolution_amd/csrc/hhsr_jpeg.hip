@@ -26,6 +26,7 @@
 // symbol counts for hhsr_jpeg_huffman).  The tables, K.2 and the header writer are in hhsr_jpeg_tables.h, free of HIP.
 #include "hhsr_common.h"
 #include "hhsr_jpeg_tables.h"
+#include "hhsr_scan.h"  // (the offsets scan below is declared there: hhsr_png.hip launches it too)
 
 // ---- tables, geometry, header writer: hhsr_jpeg_tables.h (no HIP in it) -------------------------------------------------
 using jpeg::HuffCodes;

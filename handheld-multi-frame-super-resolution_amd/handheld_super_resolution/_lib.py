@@ -91,6 +91,13 @@ _SIGS = {
     "hhsr_jpeg_histogram": [P, I, I, I, I, I, P, P, SZ, P],
     "hhsr_jpeg_huffman": [C.POINTER(C.c_uint64), I, U8P],
     "hhsr_jpeg_entropy_ex": [P, I, I, I, I, I, U8P, P, SZ, P, SZ, P, P],
+    "hhsr_png_workspace": [I, I, I, I, I, SZP, SZP, SZP],
+    "hhsr_png_filter": [P, I, I, I, I, I, I, P, SZ, P, P, SZ, P],
+    "hhsr_png_huffman": [C.POINTER(C.c_uint64), U8P],
+    "hhsr_png_deflate": [P, SZ, I, U8P, P, SZ, P, SZ, P, P],
+    "hhsr_png_file_head": [I, I, I, I, C.c_uint64, U8P, SZ, SZP],
+    "hhsr_png_file_tail": [C.c_uint32, C.c_uint64, C.c_uint32, U8P, SZ, SZP],
+    "hhsr_png_crc_combine": [C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32)],
     "hhsr_clock_probe": [P, L, P],
     "hhsr_merge_burst_chain": [PP, PP, PP, PP, I, I, I, I, I, I, I, P, P, U8P, D, I, I, P, P, P, I, I, P, I, P],
 }
@@ -105,6 +112,7 @@ NOISE_MC_CHUNK = 2048  # HHSR_NOISE_MC_CHUNK: patch pairs per workgroup of hhsr_
 MERGE_PLAN_LEN = 8  # HHSR_MERGE_PLAN_LEN: values of the record of hhsr_merge_plan_query
 MERGE_FAMILIES = ("generic", "tile", "x2_v1", "x2_mono", "x2", "x3")  # HHSR_MERGE_FAMILY_*: the record's [0]
 MERGE_GEOM_P2 = 1  # HHSR_MERGE_GEOM_P2: the record's [1]
+PNG_SPEC_BYTES = 768  # HHSR_PNG_SPEC_BYTES: the code lengths and block header of hhsr_png_huffman / hhsr_png_deflate
 
 _lib = None
 

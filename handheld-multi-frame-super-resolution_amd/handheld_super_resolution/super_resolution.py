@@ -675,16 +675,22 @@ def process(burst_path, config):
     With ``format: jpeg``, ``subsampling: 444 | 420`` (string or integer; 420 halves the chroma planes and is refused with
     ``mode: grey``) and ``huffman: standard | optimized`` (tables made for the image: a smaller file for one more
     synchronisation) choose the encoder's options; both keys are read only then, anything else is a ValueError before the
-    burst is merged."""
+    burst is merged.
+    ``config.output = {"format": "png", "dtype": "uint8" | "uint16", "filter": ..., "interval_bytes": ...}``: the result is
+    the complete PNG file of the uint8 (default) or uint16 image as a 1-D uint8 ndarray, filtered and deflate-coded on the
+    GPU (utils_image.encode_png; colour type 0 with ``mode: grey``; write it with utils_image.save_png_bytes).  ``filter``:
+    none | sub | up | average | paeth | adaptive (default); ``interval_bytes``: 1 .. 2^20 (default
+    utils_image.PNG_INTERVAL_BYTES).  ``dtype: float32``, another filter name or interval is a ValueError before the burst
+    is merged; the robustness mask stays the uint8 array it is."""
     import os
 
     from .utils_dng import infer_width, load_dng_burst, normalize_burst, normalize_packed
 
     out_cfg = config.get("output", None) or {}  # optional section, not in the reference schema
     out_format = str(out_cfg.get("format", "raw"))
-    if out_format not in ("raw", "jpeg"):
-        raise ValueError(f"config.output.format {out_format!r}: raw or jpeg")
-    out_dtype = str(out_cfg.get("dtype", "uint8" if out_format == "jpeg" else "float32"))
+    if out_format not in ("raw", "jpeg", "png"):
+        raise ValueError(f"config.output.format {out_format!r}: raw, jpeg or png")
+    out_dtype = str(out_cfg.get("dtype", "uint8" if out_format in ("jpeg", "png") else "float32"))
     if out_dtype not in ("float32", "uint8", "uint16"):
         raise ValueError(f"config.output.dtype {out_dtype!r}: float32, uint8 or uint16")
     if out_format == "jpeg" and out_dtype != "uint8":
@@ -700,6 +706,13 @@ def process(burst_path, config):
         out_huffman = jpeg_option("huffman", out_cfg.get("huffman", "standard"))
         if out_sub == "420" and config.mode == "grey":
             raise ValueError("config.output.subsampling 420 needs three components: mode grey writes one")
+    if out_format == "png":  # (refused now as well)
+        if out_dtype == "float32":
+            raise ValueError("config.output.format png holds 8- or 16-bit samples: output.dtype 'float32' contradicts it")
+        from .utils_image import png_option
+
+        out_filter = png_option("filter", out_cfg.get("filter", "adaptive"))
+        out_interval = png_option("interval_bytes", out_cfg.get("interval_bytes", None))
     if isinstance(burst_path, (str, os.PathLike)) and str(burst_path).endswith(".npz"):
         burst = dict(np.load(burst_path))
     elif isinstance(burst_path, (str, os.PathLike)):
@@ -796,6 +809,11 @@ def process(burst_path, config):
 
             output_image = encode_jpeg(out, quality=out_cfg.get("quality", 90), restart_mcus=out_cfg.get("restart_mcus", None),
                                        channels=channels, subsampling=out_sub, huffman=out_huffman)
+        elif out_format == "png":  # the whole file's bytes again: filtered and deflate-coded on the device
+            from .utils_image import encode_png
+
+            output_image = encode_png(out, bits=16 if out_dtype == "uint16" else 8, channels=channels, filter=out_filter,
+                                      interval_bytes=out_interval)
         else:
             output_image = encode_image(out, out_dtype, channels=channels).cpu().numpy()
         if acc_oriented is not None and config.robustness.save_mask:  # the reference's `.rob.png` (run_handheld.py:153-159)

@@ -493,6 +493,149 @@ def save_jpeg(file_bytes, path):
         f.write(a.tobytes())
 
 
+# ---- PNG output (include/hhsr.h "PNG output"; the reference's imsave writes its PNG on the host) ----------------------------------
+PNG_INTERVAL_BYTES = 65536  # default interval of the deflate coder, chosen by measurement (profiles/png_encode.txt: the fastest
+#                            of 4 KiB .. 256 KiB whose file is within 1 % of the largest interval's, at 8 and at 16 bits)
+PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}  # the `filter` argument of hhsr_png_filter
+
+
+def png_option(name, value):
+    """The canonical value of an encode_png / config.output option: filter -> one of PNG_FILTERS' names, interval_bytes ->
+    an int in 1 .. 2^20 (None: PNG_INTERVAL_BYTES).  Anything else is a ValueError."""
+    if name == "filter":
+        if not isinstance(value, str) or value not in PNG_FILTERS:
+            raise ValueError(f"filter={value!r}: one of {', '.join(PNG_FILTERS)}")
+        return value
+    if name == "interval_bytes":
+        if value is None:
+            return PNG_INTERVAL_BYTES
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 1 <= int(value) <= 1 << 20:
+            raise ValueError(f"interval_bytes={value!r}: an integer in 1 .. {1 << 20}")
+        return int(value)
+    raise ValueError(f"png_option: no option {name!r}")
+
+
+def png_workspace(H, W, components, bits, interval_bytes):
+    """(bytes of the filtered stream, bytes of the scratch, largest possible deflate stream) of hhsr_png_workspace."""
+    import ctypes as C
+
+    a, b, c = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+    _lib.call("hhsr_png_workspace", int(H), int(W), int(components), int(bits), int(interval_bytes), C.byref(a), C.byref(b),
+              C.byref(c))
+    return a.value, b.value, c.value
+
+
+def png_huffman(counts):
+    """hhsr_png_huffman: counts [257] (host; [256]: the number of intervals) -> spec, uint8 [_lib.PNG_SPEC_BYTES]: the
+    optimal code lengths under the 15-bit limit and the header of a dynamic-Huffman block."""
+    import ctypes as C
+
+    c = np.ascontiguousarray(counts, np.uint64)
+    if c.shape != (257,):
+        raise ValueError(f"png_huffman expects counts [257], got {c.shape}")
+    spec = np.zeros(_lib.PNG_SPEC_BYTES, np.uint8)
+    _lib.call("hhsr_png_huffman", c.ctypes.data_as(C.POINTER(C.c_uint64)), spec.ctypes.data_as(C.POINTER(C.c_uint8)))
+    return spec
+
+
+def png_file_head(H, W, components, bits, deflate_len):
+    """hhsr_png_file_head: signature, IHDR, the IDAT chunk's length and type, 78 01 — as a uint8 ndarray."""
+    import ctypes as C
+
+    buf, n = (C.c_uint8 * 64)(), C.c_size_t(0)
+    _lib.call("hhsr_png_file_head", int(H), int(W), int(components), int(bits), int(deflate_len), buf, 64, C.byref(n))
+    return np.frombuffer(buf, np.uint8, n.value).copy()
+
+
+def png_file_tail(deflate_crc, deflate_len, adler):
+    """hhsr_png_file_tail: the Adler-32, the IDAT chunk's CRC, IEND — as a uint8 ndarray."""
+    import ctypes as C
+
+    buf, n = (C.c_uint8 * 32)(), C.c_size_t(0)
+    _lib.call("hhsr_png_file_tail", int(deflate_crc), int(deflate_len), int(adler), buf, 32, C.byref(n))
+    return np.frombuffer(buf, np.uint8, n.value).copy()
+
+
+def png_crc_combine(crc_a, crc_b, len_b):
+    """hhsr_png_crc_combine: crc32(A || B) from crc32(A), crc32(B) and len(B)."""
+    import ctypes as C
+
+    out = C.c_uint32(0)
+    _lib.call("hhsr_png_crc_combine", int(crc_a), int(crc_b), int(len_b), C.byref(out))
+    return out.value
+
+
+def encode_png(img, bits=8, channels=None, filter="adaptive", interval_bytes=None, capacity=None):  # noqa: A002 (PNG's word)
+    """Device float32 [H, W, 3] or [H, W] -> the complete PNG file as a 1-D uint8 ndarray, filtered and deflate-coded on
+    the device (hhsr_png_filter, hhsr_png_deflate): the samples of encode_image(img, uint8 / uint16), colour type 2 or 0,
+    `filter` on every row ("adaptive": libpng's per-row choice), Huffman-only deflate with one code for the image and one
+    block per `interval_bytes` of the filtered stream (default PNG_INTERVAL_BYTES).  `channels=1` of an [H, W, 3] image:
+    channel 0 alone as a grey file (`mode: grey`).  Two synchronisations, as encode_jpeg(huffman="optimized"): the 2 KB of
+    byte counts are copied, hhsr_png_huffman builds the code on the host, the stream is coded into `capacity` device bytes
+    (default: the bound of hhsr_png_workspace), the three result words — length, CRC-32 of the deflate stream, Adler-32 of
+    the filtered stream, all made on the device — are read, and exactly the stream's bytes are copied; a stream that did
+    not fit is coded once more into a buffer of the reported length."""
+    if not (torch.is_tensor(img) and img.is_cuda):
+        raise RuntimeError("encode_png expects a tensor on the GPU (the HIP path has no CPU fallback)")
+    src = _lib.f32c(img)
+    if src.dim() not in (2, 3) or (src.dim() == 3 and src.shape[2] not in (1, 3)):
+        raise ValueError(f"encode_png expects [H, W] or [H, W, 3], got {tuple(src.shape)}")
+    H, W = src.shape[:2]
+    ch = 1 if src.dim() == 2 else src.shape[2]
+    och = ch if channels is None else int(channels)
+    if och not in (ch, 1):
+        raise ValueError(f"channels={channels}: {ch} (all of them) or 1 (channel 0)")
+    if bits not in (8, 16):
+        raise ValueError(f"bits={bits!r}: 8 or 16")
+    ftype = PNG_FILTERS[png_option("filter", filter)]
+    interval = png_option("interval_bytes", interval_bytes)
+    if H < 1 or W < 1 or H * (1 + W * och * bits // 8) > (1 << 31) - 1:
+        raise ValueError(f"encode_png: {H} x {W} does not fit one IDAT chunk (2^31 - 1 bytes)")
+    dev, stream = src.device, _lib.stream(src.device)
+    n, scratch_bytes, bound = png_workspace(H, W, och, bits, interval)
+    filtered = torch.empty(n, dtype=torch.uint8, device=dev)
+    scratch = torch.empty((scratch_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    counts = torch.empty(256, dtype=torch.int64, device=dev)
+    result = torch.empty(3, dtype=torch.int64, device=dev)
+    _lib.call("hhsr_png_filter", _lib.ptr(src), H, W, ch, och, bits, ftype, _lib.ptr(filtered), n, _lib.ptr(counts),
+              _lib.ptr(scratch), scratch.numel() * 8, stream)
+    c257 = np.empty(257, np.uint64)
+    c257[:256] = counts.cpu().numpy().view(np.uint64)  # (synchronises: the 2 KB of counts)
+    c257[256] = -(-n // interval)
+    spec = png_huffman(c257)
+    import ctypes as C
+
+    spec_p = spec.ctypes.data_as(C.POINTER(C.c_uint8))
+    cap = bound if capacity is None else int(capacity)
+    for _ in range(2):  # at most one retry, with the length the first pass reported
+        out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+        _lib.call("hhsr_png_deflate", _lib.ptr(filtered), n, interval, spec_p, _lib.ptr(scratch), scratch.numel() * 8,
+                  _lib.ptr(out), cap, _lib.ptr(result), stream)
+        length, crc, adler = (int(v) for v in result.cpu().numpy().view(np.uint64))  # (synchronises: the 24 bytes)
+        if length == (1 << 64) - 1:  # (cannot happen with a code built from this stream's counts)
+            raise RuntimeError("encode_png: the code lacks a byte value the stream holds")
+        if length <= cap:
+            break
+        cap = length
+    else:
+        raise RuntimeError(f"encode_png: the stream needs {length} bytes after a retry with the reported length")
+    head, tail = png_file_head(H, W, och, bits, length), png_file_tail(crc, length, adler)
+    data = np.empty(head.size + length + tail.size, np.uint8)
+    data[:head.size] = head
+    torch.from_numpy(data)[head.size:head.size + length].copy_(out[:length])  # (device -> its place in the file: one host copy)
+    data[head.size + length:] = tail
+    return data
+
+
+def save_png_bytes(file_bytes, path):
+    """The array encode_png (or process() with output.format = png) returned -> a file."""
+    a = np.asarray(file_bytes)
+    if a.dtype != np.uint8 or a.ndim != 1 or a.size < 8 or a[:8].tobytes() != b"\x89PNG\r\n\x1a\n":
+        raise ValueError("save_png_bytes expects the 1-D uint8 array of encode_png")
+    with open(path, "wb") as f:
+        f.write(a.tobytes())
+
+
 def _frame_count_denoise(image, r_acc, config, kind, strength, scale, half_index, mode=None):
     # `mode: grey` (monochrome sensors): the reference indexes the accumulated robustness with int(round(y / scale))
     # (utils_image.py:203-204, 260-261) instead of the Bayer branch's half-resolution index.  Upstream reads `mode` (and

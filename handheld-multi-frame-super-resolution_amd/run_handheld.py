@@ -9,7 +9,9 @@
 key=value  overrides, e.g. scale=2 robustness.save_mask=false; the values are read as YAML scalars, never evaluated
 
 The image is quantised on the GPU (config.output.dtype, hhsr_encode_image) and written with the standard library
-(utils_image.save_png, utils_dng.save_as_tiff).  With robustness.save_mask the accumulated-robustness mask goes to
+(utils_image.save_png, utils_dng.save_as_tiff).  With the override output.format=png and a .png outpath the PNG itself is
+coded on the GPU (utils_image.encode_png: output.dtype uint8 | uint16, output.filter, output.interval_bytes) and the returned
+bytes are written as they are.  With robustness.save_mask the accumulated-robustness mask goes to
 <outpath stem>.rob.png like upstream."""
 import argparse
 import os
@@ -46,7 +48,12 @@ def build_config(args):
                                   "with the external tools exiftool and dng_validate. Ask for .tif (the same samples) instead.")
     if suffix not in (".png", ".tif", ".tiff"):
         raise ValueError(f"--outpath {args.outpath!r}: .png (8 bits), .tif / .tiff (16 bits)")
-    config.output = {"dtype": "uint8" if suffix == ".png" else "uint16"}
+    out_cfg = config.get("output", None) or {}
+    if str(out_cfg.get("format", "raw")) == "png":  # output.format=png: process() returns the file, coded on the GPU
+        if suffix != ".png":
+            raise ValueError(f"output.format=png writes a PNG file: --outpath {args.outpath!r} does not end in .png")
+    else:
+        config.output = {"dtype": "uint8" if suffix == ".png" else "uint16"}
     noise = config.noise_model
     if (noise.get("alpha", None) is None) != (noise.get("beta", None) is None):
         raise ValueError("noise_model.alpha and noise_model.beta describe one noise profile: set both or neither")
@@ -59,12 +66,14 @@ def main(argv=None):
 
     from handheld_super_resolution import process
     from handheld_super_resolution.utils_dng import save_as_tiff
-    from handheld_super_resolution.utils_image import save_png
+    from handheld_super_resolution.utils_image import save_png, save_png_bytes
 
     image, debug_dict = process(args.impath, config)
     if config.verbose >= 1:
         print(f"writing {args.outpath} ({image.dtype}, {' x '.join(str(n) for n in image.shape)})")
-    if image.dtype.itemsize == 1:
+    if image.ndim == 1:  # output.format=png: the file's bytes, written as they are
+        save_png_bytes(image, args.outpath)
+    elif image.dtype.itemsize == 1:
         save_png(image, args.outpath)
     else:
         save_as_tiff(image, args.outpath)

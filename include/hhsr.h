@@ -733,6 +733,79 @@ int hhsr_jpeg_entropy_ex(const int16_t* coef, int H, int W, int out_channels, in
                          const uint8_t* spec, void* scratch, size_t scratch_bytes, uint8_t* scan, size_t capacity,
                          uint64_t* length, void* stream);
 
+/* ---- PNG output (run_handheld.py: imsave writes a PNG for a `.png` path, on the host) ------------------------------------
+ * The finished image as a PNG file (ISO/IEC 15948, one IDAT chunk, no interlace), filtered and deflate-coded on the device:
+ * the file's bytes are a function of the image and the options, and only counts, three result words and the file cross the
+ * host link.  The file is  head || deflate[0 .. length) || tail.  tests/png_ref.py is the NumPy / Python form of all of it.
+ *
+ *   samples      exactly hhsr_encode_image's: rint(clip(nan_to_num(x), 0, 1) * M), half to even, M = 255 (bits 8) or 65535
+ *                (bits 16, stored big-endian).  channels 1 or 3; out_channels == channels, or 1: channel 0 alone.  Colour
+ *                type 2 (out_channels 3) or 0; bpp = out_channels * bits / 8.
+ *   filtered     N = H (1 + W bpp) bytes: per row its filter type, then its bytes filtered by PNG 9.2: None (0), Sub (1),
+ *                Up (2), Average (3), Paeth (4), on bytes, modulo 256; the bytes left of a row and above row 0 are 0.
+ *                `filter` 0 .. 4: that type on every row.  5: adaptive, libpng's heuristic — per row, for each of the five
+ *                types the sum over the row's filtered bytes v of (v < 128 ? v : 256 - v); the least sum wins, ties go to
+ *                the lowest type.  Rows are independent: the row above is quantised from the image again.
+ *   counts       uint64 [256]: how often each byte value occurs in `filtered` (filter types included).  The caller adds
+ *                counts[256] = the number of intervals (one end-of-block symbol each) before hhsr_png_huffman.
+ *   spec         HOST uint8_t [HHSR_PNG_SPEC_BYTES]: [0, 257) the code lengths of the literal / end symbols 0 .. 256
+ *                (0: no code); [257] 0; [258, 260) the bit count of the block header, little-endian; [260, ...) the
+ *                header's bits, LSB first, zero-filled: BFINAL 0, BTYPE 10, HLIT 257 codes, HDIST 2 codes of length 1
+ *                (what zlib writes for a block without matches), HCLEN, the code-length code and the 259 lengths under it
+ *                (RFC 1951 3.2.7).  Code words are canonical (RFC 1951 3.2.2).
+ *   intervals    interval k covers filtered[k I, min((k + 1) I, N)), I = interval_bytes in 1 .. 2^20, and is one
+ *                dynamic-Huffman block: the header, one code per byte, the end code; bits LSB first, Huffman codes MSB
+ *                first (RFC 1951 3.1.1).  Every interval but the last has BFINAL 0 and is followed by an empty stored
+ *                block — 000, zero bits to the byte boundary, 00 00 FF FF — so every interval starts on a byte; the last has
+ *                BFINAL 1 and is zero-padded to the byte.
+ *   result       DEVICE uint64 [3]: the length of the deflate stream; its CRC-32; the Adler-32 of `filtered`.  Both
+ *                checksums are made on the device (per-interval remainders and sums, combined by a last launch).
+ *   file         head: the signature, IHDR, the IDAT length (length + 6) and type, 78 01.  tail: the Adler-32, the CRC of
+ *                the IDAT chunk — crc("IDAT" 78 01) combined with result[1] and the crc of the Adler-32's four bytes —
+ *                and IEND.
+ *   limits       the filtered stream and the bound below fit 2^31 - 1 bytes (one IDAT chunk), else error -1.
+ *                max_deflate_bytes: a code of 8 bits for 255 of the 257 symbols and 9 bits for the two rarest is a prefix
+ *                code, so the optimal code costs at most 8 T + 2 T / 257 bits for the T = N + n_int coded symbols (the two
+ *                rarest of 257 symbols occur at most 2 T / 257 times together); an interval adds at most 3700 header bits
+ *                (17 + 19 x 3 + 259 lengths of at most 7 + 7 bits), 3 bits, less than a byte of padding twice and 4 bytes:
+ *                max_deflate_bytes = ceil((8 T + floor(2 T / 257) + 1) / 8) + 468 n_int.
+ *
+ * hhsr_png_workspace (host only): *stream_bytes = N; *scratch_bytes = what hhsr_png_filter (1024 bytes per workgroup, at most
+ *   1024 of them) and hhsr_png_deflate (24 bytes per interval + 8 per 2048 intervals) need, the larger; *max_deflate_bytes.
+ * hhsr_png_filter: image DEVICE float32, compact [H][W][channels], 4-byte aligned (16-byte aligned: 16-byte loads) ->
+ *   filtered DEVICE, 16-byte aligned, filtered_bytes >= N, and counts DEVICE uint64 [256], 8-byte aligned, overwritten.
+ *   scratch DEVICE, 8-byte aligned.  Exact integer counts, the same whatever the order of the workgroups; no atomics on
+ *   device memory.  Two launches.
+ * hhsr_png_huffman (host only, HOST pointers): counts [257] -> spec.  The lengths are optimal under the 15-bit limit
+ *   (package-merge): zero counts get no code, every other symbol one, the code is complete.  Error -1 unless counts[256] and at
+ *   least one byte value are counted and the counts sum to less than 2^59.
+ * hhsr_png_deflate: filtered DEVICE (4-byte aligned, filtered_bytes = N in 1 .. 2^31 - 1) -> out[0 .. capacity) DEVICE bytes
+ *   (no alignment) and result (8-byte aligned).  The code words and the header travel as a by-value kernel argument: no
+ *   copy, no allocation, the call stays capturable, spec may be freed on return.  A stream longer than capacity is cut
+ *   there — no byte outside [out, out + capacity) is written — and all three result words are still those of the whole stream.
+ *   A byte value that spec gives no code: result[0] = UINT64_MAX, the rest unspecified.  The bytes and the result words are
+ *   the same in every run and on every stream.  Six launches: sizes, the offsets scan (three), the write pass, the checksums.
+ * hhsr_png_file_head / hhsr_png_file_tail (host only): the 43 and 20 bytes around the deflate stream; *length is set even when
+ *   capacity is too small (error -1 then).  hhsr_png_crc_combine (host only): *crc = crc32(A || B) from crc32(A), crc32(B)
+ *   and the length of B (any uint64).
+ * All: error -1 before any HIP call for a null or misaligned pointer, dimensions <= 0, channels / out_channels / bits /
+ *   filter / interval_bytes outside the above, a buffer smaller than stated, overlapping buffers, an invalid spec (a length
+ *   above 15, a code that is not complete or lacks the end symbol, an impossible header length, BFINAL set). */
+#define HHSR_PNG_SPEC_BYTES 768
+int hhsr_png_workspace(int H, int W, int out_channels, int bits, int interval_bytes, size_t* stream_bytes,
+                       size_t* scratch_bytes, size_t* max_deflate_bytes);
+int hhsr_png_filter(const float* image, int H, int W, int channels, int out_channels, int bits, int filter,
+                    uint8_t* filtered, size_t filtered_bytes, uint64_t* counts, void* scratch, size_t scratch_bytes,
+                    void* stream);
+int hhsr_png_huffman(const uint64_t* counts, uint8_t* spec);
+int hhsr_png_deflate(const uint8_t* filtered, size_t filtered_bytes, int interval_bytes, const uint8_t* spec,
+                     void* scratch, size_t scratch_bytes, uint8_t* out, size_t capacity, uint64_t* result, void* stream);
+int hhsr_png_file_head(int H, int W, int out_channels, int bits, uint64_t deflate_len, uint8_t* buf, size_t capacity,
+                       size_t* length);
+int hhsr_png_file_tail(uint32_t deflate_crc, uint64_t deflate_len, uint32_t adler, uint8_t* buf, size_t capacity,
+                       size_t* length);
+int hhsr_png_crc_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b, uint32_t* crc);
+
 /* ---- measurement support ------------------------------------------------------------------------------------------
  * Shader-clock probe: one wave that sleeps for `ticks_100mhz` ticks of the constant 100 MHz counter and stores
  * {shader cycles, 100 MHz ticks} at its start and end into out4 (DEVICE uint64[4]); launched on a side stream around a
