@@ -370,7 +370,7 @@ __device__ __forceinline__ void dodgson3(float r, int c, int len, float w[3]) {
 // values instead of 108.  Away from the left / right image border only (there the clamped taps differ per pixel and
 // the per-pixel form below is used); same operations in the same order either way: bit-identical results.
 __device__ __forceinline__ void rob_row4(const float (*win)[RF_WN][RF_WN + 2], const RobAxis& ay, const RobAxis& ax,
-                                         int wy0, int wx0, int y, int x0, int lh, int lw, const float rbk[4][3],
+                                         int wy0, int wx0, unsigned xshare, int y, int x0, int lh, int lw, const float rbk[4][3],
                                          const float d_t2[4][3], const float iss[4], float Sv, float tf, float out[4]) {
     int cy;
     float ry, wyv[3];
@@ -385,8 +385,12 @@ __device__ __forceinline__ void rob_row4(const float (*win)[RF_WN][RF_WN + 2], c
         const bool inx = rob_centre(ax, x0 + ph, lw, cx, rx);
 #pragma unroll
         for (int c = 0; c < 3; ++c) cmu[ph][c] = cmu[ph + 2][c] = INFINITY;
-        // pixel ph + 2: l + 1, centre cx + 1, same offset rx; inside the image when cx + 2 <= lw - 1 (l + 1 <= cx + 1.5)
-        if (iny && inx && cx >= 1 && cx + 2 <= lw - 1) {  // no clamped tap in x for either pixel
+        // pixel ph + 2: l + 1, centre cx + 1, same offset rx; inside the image when cx + 2 <= lw - 1 (l + 1 <= cx + 1.5).
+        // On a round-half-even tie with an even centre pixel ph + 2 rounds the other way, to cx + 2 with offset +0.5: the
+        // taps cx .. cx + 2 at (0, 1/2, 1/2) and cx + 1 .. cx + 3 at (1/2, 1/2, 0) weigh alike, unless cx + 3 is clamped to
+        // the border and takes the centre's 1/2 (robustness.py:407-413): with ff == 0.5 that tap has to be inside too.
+        // xshare = max(lw - 3 - (ff == 0.5), 0), per sub-tile: 1 <= cx <= xshare — no clamped tap in x for either pixel
+        if (iny && inx && (unsigned)(cx - 1) < xshare) {
             float wxv[3], w[3][3], wacc = 0.f;
             dodgson3(rx, cx, lw, wxv);
 #pragma unroll
@@ -570,7 +574,8 @@ __global__ void __launch_bounds__(256) k_rob_frames_row4(RobGroup gq, int lh, in
         rob_centre(ax, tsx0, lw, wx0, r_);
         wy0 = clampi(wy0, -4, lh + 4) - 1;
         wx0 = clampi(wx0, -4, lw + 4) - 1;
-        const int flags = (ay.lt ? 1 : 0) | (ay.eq ? 2 : 0) | (ay.ok ? 4 : 0) | (ax.lt ? 8 : 0) | (ax.eq ? 16 : 0) | (ax.ok ? 32 : 0);
+        const int flags = (ay.lt ? 1 : 0) | (ay.eq ? 2 : 0) | (ay.ok ? 4 : 0) | (ax.lt ? 8 : 0) | (ax.eq ? 16 : 0) | (ax.ok ? 32 : 0) |
+                          (max(lw - 3 - (ax.eq ? 1 : 0), 0) << 8);  // bits 8 ..: rob_row4's xshare (lw < 2^23)
         s_tab[fr][vv][gg][0] = make_float4(__int_as_float(ay.fi), ay.h, __int_as_float(wy0), __int_as_float(flags));
         float Sv;
         if (gq.S[fr]) {
@@ -647,7 +652,7 @@ __global__ void __launch_bounds__(256) k_rob_frames_row4(RobGroup gq, int lh, in
         if (fr + 1 < gq.n) fetch(fr + 1);
         if (!live) continue;
         float out[4];
-        rob_row4(s_g[grp][v], ay, ax, wy0, wx0, y, x0, lh, lw, rbk, d_t2, iss, Sv, (float)t, out);
+        rob_row4(s_g[grp][v], ay, ax, wy0, wx0, (unsigned)flags >> 8, y, x0, lh, lw, rbk, d_t2, iss, Sv, (float)t, out);
         rob_store4<VEC>(gq.R[fr] + o, out, x0, W);
     }
 }

@@ -122,7 +122,8 @@ def apply_noise_model(d_p, ref_means, ref_vars, std_curve, diff_curve):
 
 
 def compute_s(flow, M_th, s1, s2):
-    """robustness.py:570-612: 3x3 tile-neighbourhood flow spread."""
+    """robustness.py:570-612: 3x3 tile-neighbourhood flow spread.  The running `max` / `min` of two float32 in a Numba CUDA
+    kernel are libdevice's fmaxf / fminf: a NaN flow is skipped, hence np.fmax / np.fmin."""
     flow = np.asarray(flow, dtype=F32)
     ny, nx = flow.shape[:2]
     mx = np.full((ny, nx, 2), -np.inf, F32)
@@ -132,8 +133,8 @@ def compute_s(flow, M_th, s1, s2):
             ys, ye = max(0, -i), min(ny, ny - i)
             xs, xe = max(0, -j), min(nx, nx - j)
             src = flow[ys + i : ye + i, xs + j : xe + j]
-            mx[ys:ye, xs:xe] = np.maximum(mx[ys:ye, xs:xe], src)
-            mn[ys:ye, xs:xe] = np.minimum(mn[ys:ye, xs:xe], src)
+            mx[ys:ye, xs:xe] = np.fmax(mx[ys:ye, xs:xe], src)
+            mn[ys:ye, xs:xe] = np.fmin(mn[ys:ye, xs:xe], src)
     d = mx - mn
     m = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]).astype(F32)
     return np.where(m.astype(F64) > F64(M_th) * F64(M_th), F32(s1), F32(s2)).astype(F32)
