@@ -3,7 +3,7 @@
 // (reference kernels.py:29-243, utils_image.py:117-170 and 346-357, linalg.py:87-185).
 //
 // Bytes: 4 B/raw pixel in, 4 B/raw pixel out (16 B per quad): HBM bound.  The variance-stabilised
-// quad means are staged in LDS with a one-quad halo so each raw pixel is transformed ~1.27x.
+// quad means are staged in LDS with a one-quad halo so each raw pixel is transformed ~1.15x.
 // Arithmetic follows the reference's Numba typing: the GAT and the eigenvalue
 // roots are float64 (MI355X runs fp64 at half the fp32 vector rate, so this is affordable), storage
 // and the tensor sums are float32.
@@ -68,32 +68,25 @@ __device__ __forceinline__ float gat1(float v, double alpha, double c0, double t
     return (float)(two_over_alpha * sqrt_pos(t));
 }
 
-// Per-quad kernel covariance from the variance-stabilised quad means `sg` (LDS tile with a one-quad halo,
-// pitch SGP; (ly, lx) = the quad's position inside the tile without the halo).
+// One gradient sample of the variance-stabilised quad means `sg` (LDS tile, pitch SGP): the sample between the quads
+// (sy, sx) .. (sy + 1, sx + 1) of the tile, as the three products the structure tensor sums.
+struct CovSample {
+    float xx, xy, yy;
+};
 template <int SGP>
-__device__ __forceinline__ float4 quad_cov(const float* __restrict__ sg, int ly, int lx, int qy, int qx, int gh, int gw,
-                                           const CovParams& P) {
-    // structure tensor over the gradient samples (y-1..y, x-1..x) that exist in the [gh-1][gw-1] grid
-    float T00 = 0.f, T01 = 0.f, T11 = 0.f;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int gy_ = qy - 1 + i, gx_ = qx - 1 + j;
-            if (gy_ >= 0 && gy_ < gh - 1 && gx_ >= 0 && gx_ < gw - 1) {
-                const float g00 = sg[(ly + i) * SGP + lx + j], g01 = sg[(ly + i) * SGP + lx + j + 1];
-                const float g10 = sg[(ly + i + 1) * SGP + lx + j], g11 = sg[(ly + i + 1) * SGP + lx + j + 1];
-                // two chained float32 convs (kernels.py:97-116)
-                const float t0a = -0.5f * g00 + 0.5f * g01, t0b = -0.5f * g10 + 0.5f * g11;
-                const float t1a = 0.5f * g00 + 0.5f * g01, t1b = 0.5f * g10 + 0.5f * g11;
-                const float vx = 0.5f * t0a + 0.5f * t0b;
-                const float vy = -0.5f * t1a + 0.5f * t1b;
-                T00 += vx * vx;
-                T01 += vx * vy;
-                T11 += vy * vy;
-            }
-        }
-    }
+__device__ __forceinline__ CovSample cov_sample(const float* __restrict__ sg, int sy, int sx) {
+    const float g00 = sg[sy * SGP + sx], g01 = sg[sy * SGP + sx + 1];
+    const float g10 = sg[(sy + 1) * SGP + sx], g11 = sg[(sy + 1) * SGP + sx + 1];
+    // two chained float32 convs (kernels.py:97-116)
+    const float t0a = -0.5f * g00 + 0.5f * g01, t0b = -0.5f * g10 + 0.5f * g11;
+    const float t1a = 0.5f * g00 + 0.5f * g01, t1b = 0.5f * g10 + 0.5f * g11;
+    const float vx = 0.5f * t0a + 0.5f * t0b;
+    const float vy = -0.5f * t1a + 0.5f * t1b;
+    return {vx * vx, vx * vy, vy * vy};
+}
+
+// Structure tensor (the float32 sums of a quad's gradient samples) -> eigen-decomposition -> (k1, k2) -> covariance.
+__device__ __forceinline__ float4 cov_from_tensor(float T00, float T01, float T11, const CovParams& P) {
     // eigenvalues (linalg.py:87-130): float32 b, c; float64 discriminant and roots; stored float32
     const float b = -(T00 + T11);
     const float c = T00 * T11 - T01 * T01;
@@ -158,15 +151,55 @@ __device__ __forceinline__ float4 quad_cov(const float* __restrict__ sg, int ly,
     return o;
 }
 
+// Per-pixel kernel covariance straight from the stabilised tile `sg` (LDS tile with a one-pixel halo, pitch SGP;
+// (ly, lx) = the position inside the tile without the halo): every thread forms its four gradient samples itself.
+template <int SGP>
+__device__ __forceinline__ float4 quad_cov(const float* __restrict__ sg, int ly, int lx, int qy, int qx, int gh, int gw,
+                                           const CovParams& P) {
+    // structure tensor over the gradient samples (y-1..y, x-1..x) that exist in the [gh-1][gw-1] grid
+    float T00 = 0.f, T01 = 0.f, T11 = 0.f;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int gy_ = qy - 1 + i, gx_ = qx - 1 + j;
+            if (gy_ >= 0 && gy_ < gh - 1 && gx_ >= 0 && gx_ < gw - 1) {
+                const CovSample t = cov_sample<SGP>(sg, ly + i, lx + j);
+                T00 += t.xx;
+                T01 += t.xy;
+                T11 += t.yy;
+            }
+        }
+    }
+    return cov_from_tensor(T00, T01, T11, P);
+}
+
 // ---- fused per-frame pass over the raw image -----------------------------------------------------------------
 // Both per-frame consumers of the raw Bayer image at quad resolution — the guide-image local statistics of the
 // robustness (Alg. 7-8) and the kernel covariances (Alg. 5) — work on a quad tile with a one-quad halo.  One
-// kernel stages the tile once (4 B/pixel read instead of 8), each thread owns two quads (rows ly and ly + 8 of a
-// 32 x 16 tile: 19 % halo overhead instead of 33 %), and outputs that the caller does not need (the variances of
-// comp frames) are not written.  The stand-alone entry points hhsr_rob_stats / hhsr_cov_from_raw run the same
-// kernel with one half compiled out.
-constexpr int FS_TX = 32, FS_TY = 16, FS_P = FS_TX + 2 + 1, FS_N = (FS_TY + 2) * (FS_TX + 2);
-constexpr int FS_IT = (FS_N + 255) / 256;
+// kernel stages the tile once (4 B/pixel read instead of 8), each thread owns three quads (rows ly, ly + 8 and
+// ly + 16 of a 32 x 24 tile: 884 staged quads for 768 outputs, 1.15 each), and outputs that the caller does not need
+// (the variances of comp frames) are not written.  The stand-alone entry points hhsr_rob_stats / hhsr_cov_from_raw
+// run the same kernel with one half compiled out.
+//
+// Every gradient sample of the covariance half is formed ONCE, by the thread of its top-left quad, into an LDS tile
+// of the three products; a quad then adds the four samples around it (one sample and twelve additions per quad
+// instead of four samples: 968 -> 1253 VALU instructions per wave for 2 -> 3 quads, 484 -> 418 per quad).  The same
+// float32 products and the same order of additions: the bits of the covariances do not change
+// (tests/test_frame_stats_tiles.py holds them against a recording of the kernel before).
+//
+// Tile height, measured at 12 MP x 4 frames per launch (profiles/frame_stats_tiles.txt; 32 x 16 with every thread
+// forming its own four samples: 137 - 138 us): 32 x 16 132, 32 x 24 128 - 130, 32 x 32 134 - 137, 32 x 40 134,
+// 32 x 48 149 us.  The taller tiles stage fewer halo quads per output but run the same ~418 instructions per quad, hold
+// more LDS (32 x 32: 32 KB, five workgroups per CU) and leave the CUs a longer last round of workgroups.
+constexpr int FS_TX = 32, FS_TY = 24, FS_P = FS_TX + 2 + 1, FS_N = (FS_TY + 2) * (FS_TX + 2);
+constexpr int FS_IT = (FS_N + 255) / 256;  // staging passes of the 256 threads
+constexpr int FS_Q = FS_TY / 8;            // quads per thread: rows ly0 + 8 h
+// gradient-sample tile: sample (sy, sx) lies between the quads (sy, sx) .. (sy + 1, sx + 1) of the tile with its halo, so
+// the quad (ly, lx) sums the samples (ly .. ly + 1, lx .. lx + 1).  Odd pitch; a wave reads rows of 32 consecutive floats
+constexpr int FS_SP = FS_TX + 1, FS_SN = (FS_TY + 1) * FS_SP;
+constexpr int FS_SX = FS_TX + FS_TY + 1;   // samples of the last row and the last column: no quad of the tile is their top-left
+static_assert(FS_TY % 8 == 0 && FS_SX <= 128, "k_frame_stats: 8 rows of 32 threads; threads 128 .. form the extra samples");
 
 struct FsCfa {
     uint8_t c[4];
@@ -200,6 +233,7 @@ __global__ void __launch_bounds__(256) k_frame_stats(FrameStatsArgs A, FsFrames 
     A.covs = fr.covs[blockIdx.z];
     __shared__ float s_ch[STATS ? 3 : 1][STATS ? FS_TY + 2 : 1][FS_P];
     __shared__ float s_g[COV ? (FS_TY + 2) * FS_P : 1];
+    __shared__ float s_t[3][COV ? FS_SN : 1];  // vx vx, vx vy, vy vy of the gradient samples
     const int bid = xcd_remap(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);  // bands of tile rows per XCD
     const int qx0 = (bid % gridDim.x) * FS_TX, qy0 = (bid / gridDim.x) * FS_TY;
     const int gh = A.gh, gw = A.gw;
@@ -278,11 +312,30 @@ __global__ void __launch_bounds__(256) k_frame_stats(FrameStatsArgs A, FsFrames 
     }
     __syncthreads();
     const int lx = threadIdx.x % FS_TX, ly0 = threadIdx.x / FS_TX;
+    if (COV) {
+        // every gradient sample once: the thread of quad (ly, lx) forms sample (ly, lx), threads 128 .. the last row and
+        // column (waves 2 and 3, which have little or nothing of the last staging pass).  A sample outside the
+        // [gh-1][gw-1] grid is stored as +0: the tensor sums start at +0 and never become -0, so adding +0 leaves their
+        // bits as skipping the sample does
+        auto put = [&](int sy, int sx) {
+            const int gsy = qy0 - 1 + sy, gsx = qx0 - 1 + sx;
+            CovSample t = {0.f, 0.f, 0.f};
+            if (gsy >= 0 && gsy < gh - 1 && gsx >= 0 && gsx < gw - 1) t = cov_sample<FS_P>(s_g, sy, sx);
+            s_t[0][sy * FS_SP + sx] = t.xx;
+            s_t[1][sy * FS_SP + sx] = t.xy;
+            s_t[2][sy * FS_SP + sx] = t.yy;
+        };
+#pragma unroll
+        for (int h = 0; h < FS_Q; ++h) put(ly0 + 8 * h, lx);
+        const int e = (int)threadIdx.x - 128;
+        if (e >= 0 && e < FS_SX) put(e <= FS_TX ? FS_TY : e - (FS_TX + 1), e <= FS_TX ? e : FS_TX);
+        __syncthreads();
+    }
     const int gx = qx0 + lx;
     if (gx >= gw) return;
     const size_t plane = (size_t)gh * gw;
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
+    for (int h = 0; h < FS_Q; ++h) {
         const int ly = ly0 + 8 * h, gy = qy0 + ly;
         if (gy >= gh) break;
         const size_t o = (size_t)gy * gw + gx;
@@ -312,7 +365,20 @@ __global__ void __launch_bounds__(256) k_frame_stats(FrameStatsArgs A, FsFrames 
                 }
             }
         }
-        if (COV) A.covs[o] = quad_cov<FS_P>(s_g, ly, lx, gy, gx, gh, gw, A.P);
+        if (COV) {
+            // structure tensor over the samples (y-1..y, x-1..x), added in (i, j) order from 0 as quad_cov adds them
+            float T00 = 0.f, T01 = 0.f, T11 = 0.f;
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int k = (ly + i) * FS_SP + lx + j;
+                    T00 += s_t[0][k];
+                    T01 += s_t[1][k];
+                    T11 += s_t[2][k];
+                }
+            A.covs[o] = cov_from_tensor(T00, T01, T11, A.P);
+        }
     }
 }
 
@@ -408,6 +474,9 @@ extern "C" int hhsr_frame_stats_batch(const float* const* raws, int n_frames, in
 // The frame is its own guide image (one channel, white balance not involved: robustness.py:62-66) and the kernel
 // covariances are estimated per PIXEL from the stabilised frame itself (kernels.py:83-87): the same tile kernel with
 // pixels in the place of Bayer quads — 32 x 16 pixels per workgroup with a one-pixel halo, two pixels per thread.
+constexpr int MS_TX = 32, MS_TY = 16, MS_P = MS_TX + 2 + 1, MS_N = (MS_TY + 2) * (MS_TX + 2);
+constexpr int MS_IT = (MS_N + 255) / 256;
+
 struct MonoStatsArgs {
     const float* raw;
     int pitch, H, W;
@@ -419,34 +488,34 @@ struct MonoStatsArgs {
 
 template <bool STATS, bool COV>
 __global__ void __launch_bounds__(256) k_mono_stats(MonoStatsArgs A) {
-    __shared__ float s_v[STATS ? FS_TY + 2 : 1][FS_P];
-    __shared__ float s_g[COV ? (FS_TY + 2) * FS_P : 1];
+    __shared__ float s_v[STATS ? MS_TY + 2 : 1][MS_P];
+    __shared__ float s_g[COV ? (MS_TY + 2) * MS_P : 1];
     const int bid = xcd_remap(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
-    const int x0 = (bid % gridDim.x) * FS_TX, y0 = (bid / gridDim.x) * FS_TY;
+    const int x0 = (bid % gridDim.x) * MS_TX, y0 = (bid / gridDim.x) * MS_TY;
     const int H = A.H, W = A.W;
     const double c0 = 3.0 / 8.0 * A.P.alpha * A.P.alpha + A.P.beta;
     const double toa = 2.0 / A.P.alpha;
-    float v[FS_IT];
+    float v[MS_IT];
 #pragma unroll
-    for (int u = 0; u < FS_IT; ++u) {  // clamped pixel = the statistics' border rule (robustness.py:281-282)
-        const int p = min(threadIdx.x + 256 * u, FS_N - 1);
-        const int i = p / (FS_TX + 2), j = p - i * (FS_TX + 2);
+    for (int u = 0; u < MS_IT; ++u) {  // clamped pixel = the statistics' border rule (robustness.py:281-282)
+        const int p = min(threadIdx.x + 256 * u, MS_N - 1);
+        const int i = p / (MS_TX + 2), j = p - i * (MS_TX + 2);
         v[u] = A.raw[(size_t)clampi(y0 + i - 1, 0, H - 1) * A.pitch + clampi(x0 + j - 1, 0, W - 1)];
     }
 #pragma unroll
-    for (int u = 0; u < FS_IT; ++u) {
+    for (int u = 0; u < MS_IT; ++u) {
         const int p = threadIdx.x + 256 * u;
-        if (p < FS_N) {
-            const int i = p / (FS_TX + 2), j = p - i * (FS_TX + 2);
+        if (p < MS_N) {
+            const int i = p / (MS_TX + 2), j = p - i * (MS_TX + 2);
             if (STATS) s_v[i][j] = v[u];
             if (COV) {  // zero outside the frame: quad_cov only reads gradient samples that exist
                 const int y = y0 + i - 1, x = x0 + j - 1;
-                s_g[i * FS_P + j] = (y >= 0 && y < H && x >= 0 && x < W) ? gat1(v[u], A.P.alpha, c0, toa) : 0.f;
+                s_g[i * MS_P + j] = (y >= 0 && y < H && x >= 0 && x < W) ? gat1(v[u], A.P.alpha, c0, toa) : 0.f;
             }
         }
     }
     __syncthreads();
-    const int lx = threadIdx.x % FS_TX, ly0 = threadIdx.x / FS_TX;
+    const int lx = threadIdx.x % MS_TX, ly0 = threadIdx.x / MS_TX;
     const int gx = x0 + lx;
     if (gx >= W) return;
 #pragma unroll
@@ -471,7 +540,7 @@ __global__ void __launch_bounds__(256) k_mono_stats(MonoStatsArgs A) {
                 A.vars[o] = (float)(div_by((double)s1, 9.0, 1.0 / 9.0) - m * m);
             }
         }
-        if (COV) A.covs[o] = quad_cov<FS_P>(s_g, ly, lx, gy, gx, H, W, A.P);
+        if (COV) A.covs[o] = quad_cov<MS_P>(s_g, ly, lx, gy, gx, H, W, A.P);
     }
 }
 
@@ -488,7 +557,7 @@ extern "C" int hhsr_mono_frame_stats(const float* raw, int H, int W, int pitch, 
                : CovParams{1.0, 0.0, 0, 0, 0, 1.0, 0, 1.0, 0};
     A.P.r_D_tr = 1.0 / A.P.D_tr;
     A.P.inv_k_shrink = 1.0 / A.P.k_shrink;
-    const dim3 grid(hhsr_cdiv(W, FS_TX), hhsr_cdiv(H, FS_TY)), block(256);
+    const dim3 grid(hhsr_cdiv(W, MS_TX), hhsr_cdiv(H, MS_TY)), block(256);
     hipStream_t s = (hipStream_t)stream;
     if (means && covs) hipLaunchKernelGGL((k_mono_stats<true, true>), grid, block, 0, s, A);
     else if (means) hipLaunchKernelGGL((k_mono_stats<true, false>), grid, block, 0, s, A);
