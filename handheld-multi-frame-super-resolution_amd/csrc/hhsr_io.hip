@@ -96,25 +96,42 @@ __device__ __forceinline__ void unpack16(const uint32_t (&w)[BITS / 2], uint32_t
     }
 }
 
+// the 16 counts of a whole chunk that starts on a dword: BITS / 2 dword loads
+template <int BITS, bool BE>
+__device__ __forceinline__ void read_chunk_whole(const uint8_t* __restrict__ src, uint32_t (&p)[16]) {
+    uint32_t w[BITS / 2];
+#pragma unroll
+    for (int j = 0; j < BITS / 2; ++j) w[j] = reinterpret_cast<const uint32_t*>(src)[j];
+    unpack16<BITS, BE>(w, p);
+}
+
+// counts [0, rem) of the chunk at src -> p (p[rem .. 16) are the padding's, whatever that holds).  Reads
+// src[0 .. bytes that hold the rem pixels) and nothing else: dwords where the chunk is whole and starts on one, bytes
+// otherwise.  The ONE reader of the packed layouts: the normalisation below and the sharpness score share it.
+template <int BITS, bool BE>
+__device__ __forceinline__ void read_chunk(const uint8_t* __restrict__ src, int rem, uint32_t (&p)[16]) {
+    constexpr int NW = BITS / 2, G = BITS == 12 ? 2 : 4, GB = BITS == 12 ? 3 : BITS / 2;
+    if (rem == 16 && ((uintptr_t)src & 3) == 0) {
+        read_chunk_whole<BITS, BE>(src, p);
+        return;
+    }
+    uint32_t w[NW];
+    const int nb = BE ? (rem * BITS + 7) >> 3 : (rem + G - 1) / G * GB;  // up to the last bit / group that is used
+#pragma unroll
+    for (int j = 0; j < NW; ++j) w[j] = 0;
+#pragma unroll
+    for (int i = 0; i < 4 * NW; ++i)
+        if (i < nb) w[i >> 2] |= (uint32_t)src[i] << ((i & 3) * 8);
+    unpack16<BITS, BE>(w, p);
+}
+
 // pixels [0, rem) of the chunk at src -> v (v[rem .. 16) are the padding's, whatever that holds); x0 is a multiple of 16:
-// even pixels are CFA column 0.  Reads src[0 .. bytes that hold the rem pixels) and nothing else.
+// even pixels are CFA column 0.  Reads what read_chunk reads.
 template <int BITS, bool BE>
 __device__ __forceinline__ void normalize_chunk(const uint8_t* __restrict__ src, int rem, float (&v)[16], float b0, float b1,
                                                 float d0, float d1, float g0, float g1) {
-    constexpr int NW = BITS / 2, G = BITS == 12 ? 2 : 4, GB = BITS == 12 ? 3 : BITS / 2;
-    uint32_t w[NW], p[16];
-    if (rem == 16 && ((uintptr_t)src & 3) == 0) {
-#pragma unroll
-        for (int j = 0; j < NW; ++j) w[j] = reinterpret_cast<const uint32_t*>(src)[j];
-    } else {
-        const int nb = BE ? (rem * BITS + 7) >> 3 : (rem + G - 1) / G * GB;  // up to the last bit / group that is used
-#pragma unroll
-        for (int j = 0; j < NW; ++j) w[j] = 0;
-#pragma unroll
-        for (int i = 0; i < 4 * NW; ++i)
-            if (i < nb) w[i >> 2] |= (uint32_t)src[i] << ((i & 3) * 8);
-    }
-    unpack16<BITS, BE>(w, p);
+    uint32_t p[16];
+    read_chunk<BITS, BE>(src, rem, p);
 #pragma unroll
     for (int k = 0; k < 16; k += 2) {
         v[k] = ((float)p[k] - b0) / d0 * g0;
@@ -222,6 +239,273 @@ extern "C" int hhsr_normalize_raw_packed(const uint8_t* raw, int n_frames, int H
         HHSR_PACKED(HHSR_PACK_BE14, 14, true)
     }
 #undef HHSR_PACKED
+    HHSR_LAUNCHED();
+}
+
+// ---- sharpness score of the candidate reference frames (include/hhsr.h: "reference selection") --------------------------
+// One pass over the frames as they lie in memory — float32, uint16 counts or the packed bytes — 4, 2 or 1.25 - 1.75 bytes
+// per pixel in, one double per workgroup out: HBM bound.
+//
+// Tiling (the same for every format, so that the float64 sum has ONE order per (H, W)):
+//   unit       16 pixels x 2 rows = SHARP_UNIT_Q (8) quads of one quad row: one thread, one packed chunk per row
+//   wave       64 units side by side, of which it OWNS the first SHARP_WAVE_UNITS (63): 504 quads of one quad row.  The quad
+//              right of a unit is the neighbour lane's first (one shuffle); lane 63 only supplies that quad to lane 62 — its
+//              unit is the next workgroup's lane 0, read here a second time from cache (1 / 63 of the frame).  A wave walks
+//              SHARP_BAND (8) quad rows downwards, carrying the green values of the row above in registers, and reads the
+//              quad row below its band once more (1 / 8, rows that the wave below reads at about the same time).
+//   workgroup  4 waves below each other: SHARP_TILE_QW x SHARP_TILE_QH = 504 x 32 quads (1008 x 64 pixels);
+//              at 12 MP 4 x 47 workgroups per frame.
+// Where every unit of a wave is whole and every row starts on 16 bytes (packed: a dword) — all of a 4000-pixel row, any
+// compact or 16-byte padded frame — the wave's loads are 16-byte vectors (dwords) with no branch around them; any other
+// wave (the row's tail, an odd base or stride) takes the path that decides per unit and reads item by item.  Both paths
+// add the same terms in the same order.
+// A thread adds its terms in float64 in the order (quad row; quad; dx then dy), the wave adds its lanes by the shuffle
+// tree below, thread 0 the four waves in ascending order; k_sharpness_sum adds a frame's workgroups: lane l of one wave
+// takes every 64th partial from l on in ascending order, then the same tree.
+#define SHARP_UNIT_Q 8
+#define SHARP_BAND 8
+#define SHARP_WAVES 4
+#define SHARP_WAVE_UNITS (HHSR_WAVE - 1)
+#define SHARP_TILE_QW (SHARP_UNIT_Q * SHARP_WAVE_UNITS)
+#define SHARP_TILE_QH (SHARP_BAND * SHARP_WAVES)
+#define SHARP_FMT_F32 0
+#define SHARP_FMT_U16 (-1)
+
+struct SharpFrames {
+    const uint8_t* p[HHSR_MAX_BATCH];
+};
+
+// values [0, rem) of unit u of the row at `row` -> v (the rest 0).  16-byte loads (packed: dwords) where the unit is whole
+// and starts on 16 bytes (a dword), item by item otherwise: the same values.  WHOLE: the caller has checked both.
+template <int FMT, bool WHOLE>
+__device__ __forceinline__ void sharp_load(const uint8_t* __restrict__ row, int u, int rem, float (&v)[16]) {
+    if constexpr (FMT == SHARP_FMT_F32) {
+        const float* __restrict__ src = reinterpret_cast<const float*>(row) + (size_t)u * 16;
+        if (WHOLE || (rem == 16 && ((uintptr_t)src & 15) == 0)) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float4 q = reinterpret_cast<const float4*>(src)[j];
+                v[4 * j] = q.x, v[4 * j + 1] = q.y, v[4 * j + 2] = q.z, v[4 * j + 3] = q.w;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) v[k] = k < rem ? src[k] : 0.0f;
+        }
+    } else if constexpr (FMT == SHARP_FMT_U16) {
+        const uint16_t* __restrict__ src = reinterpret_cast<const uint16_t*>(row) + (size_t)u * 16;
+        if (WHOLE || (rem == 16 && ((uintptr_t)src & 15) == 0)) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const uint4 q = reinterpret_cast<const uint4*>(src)[j];
+                const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    v[8 * j + 2 * k] = (float)(w[k] & 0xffffu);
+                    v[8 * j + 2 * k + 1] = (float)(w[k] >> 16);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) v[k] = k < rem ? (float)src[k] : 0.0f;
+        }
+    } else {
+        constexpr int BITS = 10 + 2 * ((FMT - 1) % 3);
+        constexpr bool BE = FMT >= HHSR_PACK_BE10;
+        uint32_t p[16];
+        if constexpr (WHOLE) {
+            read_chunk_whole<BITS, BE>(row + (size_t)u * (2 * BITS), p);
+#pragma unroll
+            for (int k = 0; k < 16; ++k) v[k] = (float)p[k];
+        } else {
+            read_chunk<BITS, BE>(row + (size_t)u * (2 * BITS), rem, p);
+#pragma unroll
+            for (int k = 0; k < 16; ++k) v[k] = k < rem ? (float)p[k] : 0.0f;
+        }
+    }
+}
+
+// green value of quad k of a unit from its two rows.  (a, b): the two CFA positions that are green, a < b, in cell order
+// (row & 1) * 2 + (col & 1); a < 0: no CFA, the mean of the four.
+__device__ __forceinline__ float sharp_green(const float (&t)[16], const float (&b)[16], int k, int pa, int pb) {
+    const float t0 = t[2 * k], t1 = t[2 * k + 1], b0 = b[2 * k], b1 = b[2 * k + 1];
+    if (pa < 0) return ((t0 + t1) + (b0 + b1)) * 0.25f;
+    const float va = pa == 0 ? t0 : (pa == 1 ? t1 : b0);
+    const float vb = pb == 1 ? t1 : (pb == 2 ? b0 : b1);
+    return (va + vb) * 0.5f;
+}
+
+__device__ __forceinline__ double sharp_wave_sum(double v) {
+#pragma unroll
+    for (int o = HHSR_WAVE / 2; o > 0; o >>= 1) v += __shfl_down(v, o, HHSR_WAVE);
+    return v;  // (lane 0 holds the total)
+}
+
+// green values of quad row qy for this thread's unit (g[0 .. 8)) and of the quad right of it (g[8]: the neighbour lane's
+// first; lane 63 has none and owns no term).  Quads past the row's end are 0 and enter no term.  All 64 lanes of the wave
+// call it (the shuffle).
+template <int FMT, bool WHOLE>
+__device__ __forceinline__ void sharp_row(const uint8_t* __restrict__ frame, size_t row_bytes, int qy, int u, int rem, int pa,
+                                          int pb, float (&g)[SHARP_UNIT_Q + 1]) {
+    const uint8_t* __restrict__ top = frame + (size_t)(2 * qy) * row_bytes;
+    const uint8_t* __restrict__ bot = top + row_bytes;
+    float t[16], b[16];
+    if (WHOLE || rem > 0) {
+        sharp_load<FMT, WHOLE>(top, u, rem, t);
+        sharp_load<FMT, WHOLE>(bot, u, rem, b);
+#pragma unroll
+        for (int k = 0; k < SHARP_UNIT_Q; ++k) g[k] = sharp_green(t, b, k, pa, pb);
+    } else {
+#pragma unroll
+        for (int k = 0; k < SHARP_UNIT_Q; ++k) g[k] = 0.0f;
+    }
+    g[SHARP_UNIT_Q] = __shfl_down(g[0], 1, HHSR_WAVE);
+}
+
+// the terms of one wave's band, quad rows [y0, y0 + SHARP_BAND) of unit u, whose first quad is q0 (>= w: the thread owns no
+// term).  The row below is loaded before the row's terms are added; past the last quad row the last one is loaded again
+// (from cache) and enters no term, so that the loop has no branch around its loads and they can be issued rows ahead.
+template <int FMT, bool WHOLE>
+__device__ __forceinline__ double sharp_band(const uint8_t* __restrict__ frame, size_t row_bytes, int h, int w, int y0, int u,
+                                             int rem, int q0, int pa, int pb) {
+    double acc = 0.0;
+    float cur[SHARP_UNIT_Q + 1], nxt[SHARP_UNIT_Q + 1];
+    sharp_row<FMT, WHOLE>(frame, row_bytes, y0, u, rem, pa, pb, cur);
+    for (int i = 0; i < SHARP_BAND; ++i) {  // (rolled: unrolling by 2 or 8 measured the same or slower, profiles/ref_select.txt)
+        const int qy = y0 + i;
+        const bool in = qy < h, below = qy + 1 < h;  // (uniform)
+        sharp_row<FMT, WHOLE>(frame, row_bytes, below ? qy + 1 : h - 1, u, rem, pa, pb, nxt);
+#pragma unroll
+        for (int k = 0; k < SHARP_UNIT_Q; ++k) {
+            if (in && q0 + k < w - 1) {
+                const float d = cur[k + 1] - cur[k];
+                acc += (double)(d * d);
+            }
+            if (below && q0 + k < w) {
+                const float d = nxt[k] - cur[k];
+                acc += (double)(d * d);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k <= SHARP_UNIT_Q; ++k) cur[k] = nxt[k];
+    }
+    return acc;
+}
+
+// grid (tiles along x, tiles along y, frames); part[(frame * gridDim.y + tile_y) * gridDim.x + tile_x]
+template <int FMT>
+__global__ void __launch_bounds__(SHARP_WAVES* HHSR_WAVE) k_sharpness(SharpFrames F, int H, int W, size_t row_bytes, int pa,
+                                                                       int pb, double* __restrict__ part) {
+    __shared__ double sm[SHARP_WAVES];
+    const int lane = threadIdx.x & (HHSR_WAVE - 1), wv = threadIdx.x / HHSR_WAVE;
+    const int h = H >> 1, w = W >> 1;
+    const int u0 = blockIdx.x * SHARP_WAVE_UNITS, u = u0 + lane;
+    const int rem = W - 16 * u < 16 ? W - 16 * u : 16;          // <= 0: the unit lies past the row's end
+    const int q0 = lane < SHARP_WAVE_UNITS ? u * SHARP_UNIT_Q : w;  // lane 63 is the next workgroup's lane 0: no term here
+    const int y0 = blockIdx.y * SHARP_TILE_QH + wv * SHARP_BAND;
+    const uint8_t* __restrict__ frame = F.p[blockIdx.z];
+    double acc = 0.0;
+    if (y0 < h) {  // (uniform per wave)
+        // every unit of the wave whole and on 16 bytes (packed: a dword): the loads need no branch; lanes past the row's
+        // end then load the workgroup's first unit (it exists and is whole) and own no term
+        constexpr uintptr_t align = FMT > 0 ? 3 : 15;
+        const bool whole = (rem == 16 || rem <= 0) && ((((uintptr_t)frame) | row_bytes) & align) == 0;
+        if (__all(whole))
+            acc = sharp_band<FMT, true>(frame, row_bytes, h, w, y0, rem > 0 ? u : u0, 16, q0, pa, pb);
+        else
+            acc = sharp_band<FMT, false>(frame, row_bytes, h, w, y0, u, rem, q0, pa, pb);
+    }
+    acc = sharp_wave_sum(acc);
+    if (lane == 0) sm[wv] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = sm[0];
+#pragma unroll
+        for (int k = 1; k < SHARP_WAVES; ++k) s += sm[k];
+        part[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = s;
+    }
+}
+
+// one wave per frame: its `tiles` partials -> scores[frame]
+__global__ void __launch_bounds__(HHSR_WAVE) k_sharpness_sum(const double* __restrict__ part, int tiles,
+                                                              double* __restrict__ scores) {
+    const double* __restrict__ row = part + (size_t)blockIdx.x * tiles;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < tiles; i += HHSR_WAVE) acc += row[i];
+    acc = sharp_wave_sum(acc);
+    if (threadIdx.x == 0) scores[blockIdx.x] = acc;
+}
+
+// workgroups of one frame; 0 where the sizes are refused
+static int64_t sharp_tiles(int H, int W, int* tx, int* ty) {
+    if (H <= 0 || W <= 0 || (H & 1) || (W & 1)) return 0;
+    if (W > INT32_MAX - 2 * 16 * HHSR_WAVE) return 0;        // 16 u of the lanes behind a row's last unit, in 32 bits
+    const int64_t x = ((int64_t)(W / 2) + SHARP_TILE_QW - 1) / SHARP_TILE_QW;
+    const int64_t y = ((int64_t)(H / 2) + SHARP_TILE_QH - 1) / SHARP_TILE_QH;
+    if (y > 65535 || x * y > INT32_MAX) return 0;            // the grid's y size; the partials of a frame as an int
+    *tx = (int)x, *ty = (int)y;
+    return x * y;
+}
+
+extern "C" int hhsr_sharpness_workspace(int H, int W, int n_frames, size_t* bytes) {
+    HHSR_ARG(bytes != nullptr);
+    HHSR_ARG(n_frames >= 1 && n_frames <= HHSR_MAX_BATCH);
+    int tx, ty;
+    const int64_t tiles = sharp_tiles(H, W, &tx, &ty);
+    HHSR_ARG(tiles > 0);
+    *bytes = (size_t)tiles * n_frames * sizeof(double);
+    return 0;
+}
+
+extern "C" int hhsr_frame_sharpness(const void* const* frames, int n_frames, int H, int W, int64_t row_bytes, int format,
+                                    const uint8_t* cfa, void* workspace, size_t workspace_bytes, double* scores,
+                                    void* stream) {
+    HHSR_ARG(frames && workspace && scores);
+    HHSR_ARG(n_frames >= 1 && n_frames <= HHSR_MAX_BATCH);
+    int tx, ty;
+    const int64_t tiles = sharp_tiles(H, W, &tx, &ty);
+    HHSR_ARG(tiles > 0);
+    int pa = -1, pb = -1;
+    if (cfa) {
+        int greens = 0;
+        for (int k = 0; k < 4; ++k) {
+            HHSR_ARG(cfa[k] <= 2);
+            if (cfa[k] == 1) {
+                (greens == 0 ? pa : pb) = k;
+                ++greens;
+            }
+        }
+        HHSR_ARG(greens == 2);
+    }
+    HHSR_ARG(format == SHARP_FMT_F32 || format == SHARP_FMT_U16 || (format >= HHSR_PACK_MIPI10 && format <= HHSR_PACK_BE14));
+    const int item = format == SHARP_FMT_F32 ? 4 : (format == SHARP_FMT_U16 ? 2 : 1);
+    const int64_t need = format > 0 ? packed_row_bytes(W, format) : (int64_t)item * W;
+    HHSR_ARG(row_bytes >= need && row_bytes % item == 0);
+    HHSR_ARG(row_bytes <= INT64_MAX / H);  // the byte offset of the last row
+    for (int n = 0; n < n_frames; ++n) HHSR_ARG(frames[n] != nullptr && ((uintptr_t)frames[n] & (item - 1)) == 0);
+    HHSR_ARG(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)scores & 7) == 0);
+    HHSR_ARG(workspace_bytes / sizeof(double) / n_frames >= (size_t)tiles);
+    SharpFrames F;
+    for (int n = 0; n < HHSR_MAX_BATCH; ++n) F.p[n] = (const uint8_t*)frames[n < n_frames ? n : 0];
+    const dim3 grid(tx, ty, n_frames);
+    hipStream_t s = (hipStream_t)stream;
+    double* part = (double*)workspace;
+#define HHSR_SHARP(ID)                                                                                                \
+    case ID:                                                                                                          \
+        hipLaunchKernelGGL((k_sharpness<ID>), grid, dim3(SHARP_WAVES* HHSR_WAVE), 0, s, F, H, W, (size_t)row_bytes, pa, \
+                           pb, part);                                                                                 \
+        break;
+    switch (format) {
+        HHSR_SHARP(SHARP_FMT_F32)
+        HHSR_SHARP(SHARP_FMT_U16)
+        HHSR_SHARP(HHSR_PACK_MIPI10)
+        HHSR_SHARP(HHSR_PACK_MIPI12)
+        HHSR_SHARP(HHSR_PACK_MIPI14)
+        HHSR_SHARP(HHSR_PACK_BE10)
+        HHSR_SHARP(HHSR_PACK_BE12)
+        HHSR_SHARP(HHSR_PACK_BE14)
+    }
+#undef HHSR_SHARP
+    hipLaunchKernelGGL(k_sharpness_sum, dim3(n_frames), dim3(HHSR_WAVE), 0, s, (const double*)part, (int)tiles, scores);
     HHSR_LAUNCHED();
 }
 

@@ -5,6 +5,6 @@ Host code is Python on PyTorch-ROCm tensors; every stage is a hand-written HIP k
 reached through the C ABI of libhhsr_hip.so (include/hhsr.h).  Importing the package does not need a
 GPU; calling into the hot path without one (or without the built library) raises RuntimeError."""
 from .config import Config, OmegaConf, default_config  # noqa: F401
-from .super_resolution import process, main, prepare_config, BurstPipeline  # noqa: F401
+from .super_resolution import process, main, prepare_config, BurstPipeline, select_reference  # noqa: F401
 
-__all__ = ["process", "main", "prepare_config", "BurstPipeline", "Config", "OmegaConf", "default_config"]
+__all__ = ["process", "main", "prepare_config", "BurstPipeline", "select_reference", "Config", "OmegaConf", "default_config"]

@@ -51,6 +51,8 @@ _SIGS = {
     "hhsr_normalize_raw_u16": [P, I, I, I, I, U8P, DP, D, DP, P, P],
     "hhsr_normalize_raw_packed": [P, I, I, I, L, L, I, U8P, DP, D, DP, P, P],
     "hhsr_packed_row_bytes": [I, I, I64P],
+    "hhsr_sharpness_workspace": [I, I, I, SZP],
+    "hhsr_frame_sharpness": [PP, I, I, I, L, I, U8P, P, SZ, P, P],
     "hhsr_rob_upscale": [P, I, I, P, I, I, I, P, P],
     "hhsr_rob_s": [P, I, I, D, F, F, P, I, I, P],
     "hhsr_rob_sigma": [P, P, I, I, P, I, P, P, P],

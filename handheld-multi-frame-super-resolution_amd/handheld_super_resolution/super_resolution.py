@@ -605,6 +605,87 @@ def main(ref_img, comp_imgs, config, *, _no_runner=False):
     return num, debug_dict
 
 
+REFERENCE_SELECT = ("first", "sharpest")
+REFERENCE_CANDIDATES = 3  # HDR+ picks among the first three frames: a later base frame costs shutter lag
+
+
+def reference_options(config):
+    """(select, candidates) of the optional section config.reference = {"select": "first" | "sharpest", "candidates": 3}
+    (not in the reference schema, like config.output; absent: ("first", 3)).  ValueError for anything else."""
+    sec = config.get("reference", None) or {}
+    select = str(sec.get("select", "first"))
+    if select not in REFERENCE_SELECT:
+        raise ValueError(f"config.reference.select {select!r}: first or sharpest")
+    cand = sec.get("candidates", REFERENCE_CANDIDATES)
+    if isinstance(cand, bool) or not isinstance(cand, (int, np.integer)) or cand < 1:
+        raise ValueError(f"config.reference.candidates {cand!r}: an integer >= 1")
+    return select, int(cand)
+
+
+def candidate_count(config, n_burst):
+    """How many of a burst's n_burst frames are candidates: config.reference.candidates clamped to the burst's length."""
+    return max(1, min(reference_options(config)[1], int(n_burst)))
+
+
+def pick_reference(scores):
+    """Index of the largest finite score, ties to the lowest index; a non-finite score never wins; 0 if none is finite."""
+    best, arg = -np.inf, 0
+    for i, s in enumerate(np.asarray(scores, np.float64).reshape(-1)):
+        if np.isfinite(s) and s > best:
+            best, arg = s, i
+    return arg
+
+
+def select_reference(ref, comp, config, cfa_pattern=None, packing=None, width=None):
+    """(index, scores): the sharpest of the burst's first config.reference.candidates frames (clamped to the burst's
+    length), [ref, comp[0], ..., comp[K - 2]] in burst order, scored on the GPU by utils_image.frame_sharpness; `index` by
+    pick_reference, `scores` a float64 ndarray [K].  Host frames are uploaded in their own form — float32, uint16 counts
+    or, with `packing`, the packed uint8 rows — and scored as they are: integer counts are not normalised first.
+    `cfa_pattern`: the burst's (default: config.exif's); ignored with `mode: grey`, whose score has no CFA.  One host
+    synchronisation (the scores decide what is uploaded and merged next)."""
+    from .utils_image import frame_sharpness
+
+    k = candidate_count(config, 1 + len(comp))
+    dev = _device()
+    frames = []
+    for f in [ref] + [comp[i] for i in range(k - 1)]:
+        if not torch.is_tensor(f):
+            a = np.asarray(f)
+            if np.issubdtype(a.dtype, np.integer) and packing is None and a.dtype != np.uint16:
+                if a.size and (int(a.min()) < 0 or int(a.max()) > 65535):
+                    raise ValueError("sensor counts outside the uint16 range")
+                a = a.astype(np.uint16)
+            elif not np.issubdtype(a.dtype, np.integer):
+                a = a.astype(np.float32, copy=False)
+            f = torch.as_tensor(np.ascontiguousarray(a))
+        if f.dtype.is_floating_point and f.dtype != torch.float32:
+            f = f.to(torch.float32)
+        frames.append(f.to(dev, non_blocking=True))
+    if config.mode == "grey":
+        cfa = None
+    else:
+        cfa = cfa_pattern if cfa_pattern is not None else config.exif.cfa_pattern
+        cfa = np.asarray(cfa).tolist()
+    if packing is not None:
+        packing = np.asarray(packing).item()
+        width = None if width is None else int(np.asarray(width))
+    scores = frame_sharpness(frames, cfa, packing=packing, width=width).cpu().numpy()
+    return pick_reference(scores), scores
+
+
+def reorder_burst(ref, comp, index):
+    """(ref, comp) with frame `index` of [ref, comp[0], ...] as the reference frame; the other frames keep their order."""
+    if index == 0:
+        return ref, comp
+    j = index - 1
+    if torch.is_tensor(comp):
+        return comp[j], torch.cat([torch.as_tensor(ref).to(comp)[None], comp[:j], comp[j + 1:]])
+    if isinstance(comp, np.ndarray):
+        return comp[j], np.concatenate([np.asarray(ref, dtype=comp.dtype)[None], comp[:j], comp[j + 1:]])
+    comp = list(comp)
+    return comp[j], [ref] + comp[:j] + comp[j + 1:]
+
+
 def prepare_config(config, ref_raw, alpha=None, beta=None, cfa_pattern=None, white_balance=None, iso=100,
                    std_curve=None, diff_curve=None, shape=None):
     """The parameter derivation process() performs between loading the burst and calling main()
@@ -681,7 +762,17 @@ def process(burst_path, config):
     GPU (utils_image.encode_png; colour type 0 with ``mode: grey``; write it with utils_image.save_png_bytes).  ``filter``:
     none | sub | up | average | paeth | adaptive (default); ``interval_bytes``: 1 .. 2^20 (default
     utils_image.PNG_INTERVAL_BYTES).  ``dtype: float32``, another filter name or interval is a ValueError before the burst
-    is merged; the robustness mask stays the uint8 array it is."""
+    is merged; the robustness mask stays the uint8 array it is.
+    ``config.reference = {"select": "first" | "sharpest", "candidates": 3}`` (optional; absent or "first": ``ref`` is the
+    base frame, as in the reference, which takes file 0 — nothing below runs then): with "sharpest" the first ``candidates``
+    frames of the burst (clamped to its length) are scored on the GPU in the form they come in (select_reference,
+    hhsr_frame_sharpness), the sharpest becomes ``ref`` and the others keep their order as ``comp``; everything derived from
+    the reference frame — its brightness and the SNR-based parameters, the early normalisation of an integer burst —
+    follows the chosen frame.  ``debug_dict["reference index"]`` is its position in the original burst,
+    ``debug_dict["sharpness"]`` the candidates' scores (float64 ndarray).  The candidates are uploaded once for the score
+    and again by main().  For a folder of .dng files the frame arrays are reordered; the tags (noise profile, ISO,
+    orientation, colour matrix) stay those of file 0.  Another ``select`` or ``candidates`` < 1 is a ValueError before
+    anything is uploaded."""
     import os
 
     from .utils_dng import infer_width, load_dng_burst, normalize_burst, normalize_packed
@@ -713,6 +804,7 @@ def process(burst_path, config):
 
         out_filter = png_option("filter", out_cfg.get("filter", "adaptive"))
         out_interval = png_option("interval_bytes", out_cfg.get("interval_bytes", None))
+    ref_select, _ = reference_options(config)  # (refused now as well)
     if isinstance(burst_path, (str, os.PathLike)) and str(burst_path).endswith(".npz"):
         burst = dict(np.load(burst_path))
     elif isinstance(burst_path, (str, os.PathLike)):
@@ -735,6 +827,11 @@ def process(burst_path, config):
         burst.setdefault("cfa_pattern", [[0, 1], [1, 2]])
         burst.setdefault("white_balance", [1.0, 1.0, 1.0])
     ref_raw, raw_comp = burst["ref"], burst["comp"]
+    ref_index = ref_scores = None
+    if ref_select == "sharpest":  # the chosen frame is `ref` from here on
+        ref_index, ref_scores = select_reference(ref_raw, raw_comp, config, burst["cfa_pattern"], burst.get("packing", None),
+                                                 burst.get("width", None))
+        ref_raw, raw_comp = reorder_burst(ref_raw, raw_comp, ref_index)
     if not torch.is_tensor(ref_raw) and np.issubdtype(np.asarray(ref_raw).dtype, np.integer):
         # sensor counts + metadata: the normalisation / white balance of utils_dng.py:149-160, on the GPU.  The
         # reference frame now (its brightness picks the SNR-based parameters); the other frames stay integer host arrays
@@ -775,6 +872,9 @@ def process(burst_path, config):
                    int(burst.get("iso", 100)), std_curve, diff_curve,
                    shape=tuple(ref_raw.shape))
     out, debug_dict = main(ref_raw, raw_comp, config)
+    if ref_index is not None:
+        debug_dict["reference index"] = int(ref_index)
+        debug_dict["sharpness"] = np.asarray(ref_scores, np.float64)
 
     # ---- after the path (reference super_resolution.py:303-356), on the device --------------------------------------
     from . import raw2rgb

@@ -457,6 +457,48 @@ int hhsr_normalize_raw_packed(const uint8_t* raw, int n_frames, int H, int W, in
                               const double* white_balance, float* out, void* stream);
 int hhsr_packed_row_bytes(int W, int packing, int64_t* bytes_out);
 
+/* ---- reference selection: the sharpness score of a burst's candidate base frames ---------------------------------------
+ * The reference takes file 0 of the burst as its base frame (utils_dng.py:77); the burst pipelines the algorithm comes from
+ * (HDR+; Wronski et al.) take the sharpest of the first few frames, scored by the gradients of the raw green channel.  No
+ * counterpart in the reference.  The score, stated once (tests/sharpness_ref.py is its NumPy form):
+ *
+ *   frame     [H][W], H and W even; h = H / 2, w = W / 2.
+ *   value     v(y, x): a float32 frame's value itself; for uint16 or packed counts float32(count), NOT normalised — only
+ *             the order of a burst's frames matters, and black level, white level and green gain are common to them.
+ *   green     Bayer: g(qy, qx) = (v_a + v_b) * 0.5f, a < b the two positions of the 2 x 2 CFA cell whose entry is 1, in cell
+ *             order (row & 1) * 2 + (col & 1).  No CFA (cfa NULL, `mode: grey`): g = ((v00 + v01) + (v10 + v11)) * 0.25f.
+ *   terms     dx = g(qy, qx + 1) - g(qy, qx) for qx < w - 1, dy = g(qy + 1, qx) - g(qy, qx) for qy < h - 1; a term is d * d,
+ *             the float32 subtraction and the float32 multiplication, not contracted.
+ *   score     the sum of all h (w - 1) + (h - 1) w terms in float64.  A 2 x 2 frame scores 0; NaN and Inf propagate.
+ *
+ * The order of the float64 additions is a function of (H, W) alone: a thread adds the terms of its 8 quads per quad row in
+ * a fixed order, a wave its lanes and a workgroup its waves by a fixed tree, every workgroup stores one double into the
+ * workspace and a second kernel adds a frame's partials in a fixed order.  No float64 atomics.  So a frame's score is
+ * reproducible bit for bit and does not depend on its alignment, its row stride, n_frames, its place in `frames`, its
+ * format (the same counts as float32, uint16 or packed bytes) or on which load path a row takes: 16-byte vectors (packed
+ * rows: dwords) where the 16-pixel pieces of a wave's 1024 pixels are all whole and base and row_bytes are multiples of 16
+ * (packed: of 4), a decision per piece and item-by-item reads elsewhere.  The order itself is not part of
+ * the contract (it moves the score by float64 rounding: at most n_terms 2^-52 relative).
+ *
+ * hhsr_sharpness_workspace (host only, no HIP call): bytes of the partial sums, n_frames doubles per workgroup of 1008 x 64
+ *   pixels; never smaller for a larger H, a larger W or more frames.
+ * hhsr_frame_sharpness: frames HOST table of n_frames (1 .. HHSR_MAX_BATCH) DEVICE pointers, one shape and format; row y
+ *   of frame n starts at (char*)frames[n] + y * row_bytes.  format: 0 float32, -1 uint16, or HHSR_PACK_* for packed uint8 rows
+ *   (the layouts of hhsr_normalize_raw_packed, read by the same code).  cfa: HOST, 4 bytes, or NULL for a monochrome
+ *   sensor.  scores: DEVICE double[n_frames].  workspace: DEVICE, 8-byte aligned, at least the bytes
+ *   hhsr_sharpness_workspace reports; contents are scratch.  Every byte of a frame's rows is read once (a workgroup reads the
+ *   16 pixels right of it and the 2 rows below each of its 4 bands once more, from cache: 1 / 63 and 1 / 8 of the frame);
+ *   the bytes between a row's end and the next row are not read.
+ *   Two launches on `stream`, no allocation, copy or synchronisation: capturable.
+ *   Error -1, before any HIP call: a null pointer (cfa excepted), n_frames outside 1 .. HHSR_MAX_BATCH, H or W odd or <= 0,
+ *   W > INT32_MAX - 2048 or H > 4194240 (the kernel's 32-bit pixel indices and its grid), a cfa without exactly two entries
+ *   equal to 1 or with an entry above 2, an unknown format, row_bytes below the row's bytes (4 W, 2 W,
+ *   hhsr_packed_row_bytes) or not a multiple of the item size, H row_bytes beyond int64, a frame pointer not aligned to its
+ *   item (4, 2, 1 bytes), scores or workspace off 8 bytes, a workspace that is too small. */
+int hhsr_sharpness_workspace(int H, int W, int n_frames, size_t* bytes);
+int hhsr_frame_sharpness(const void* const* frames, int n_frames, int H, int W, int64_t row_bytes, int format,
+                         const uint8_t* cfa, void* workspace, size_t workspace_bytes, double* scores, void* stream);
+
 /* ---- after the path: frame-count denoisers, postprocess, orientation — on the device -------------
  * hhsr_frame_count_denoise: utils_image.py:174-309.  image / out float32 [H][W][3] (the merged image), acc_r float32
  * [ah][aw] (accumulated robustness).  kind 0 = median (strength_max = radius_max <= 7: the reference's 16 x 16 sample
