@@ -33,7 +33,8 @@ SOURCES = {
     "hhsr_post.hip": ["-ffp-contract=off"],
     "hhsr_tonemap.hip": ["-ffp-contract=off"],  # the Mertens weight maps are a decision stage (exact float32 association)
     "hhsr_noise.hip": ["-ffp-contract=off"],    # the Monte-Carlo stream is stated without fused multiply-adds (hhsr.h)
-    "hhsr_encode.hip": ["-ffp-contract=off"],   # quantisation: one float32 multiply, then rint — a decision stage
+    "hhsr_noise_profile.hip": ["-ffp-contract=off"],  # residuals and sums stated without contraction; the host fit too
+    "hhsr_encode.hip":["-ffp-contract=off"],   # quantisation: one float32 multiply, then rint — a decision stage
     "hhsr_jpeg.hip": ["-ffp-contract=off"],     # the sample rule above, then the DCT and rint(c / Q): stated without contraction
     "hhsr_png.hip": ["-ffp-contract=off"],      # the same sample rule; everything behind it is integer
 }

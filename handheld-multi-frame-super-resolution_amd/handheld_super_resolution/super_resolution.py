@@ -686,6 +686,32 @@ def reorder_burst(ref, comp, index):
     return comp[j], [ref] + comp[:j] + comp[j + 1:]
 
 
+def estimate_burst_profile(ref_raw, raw_comp, burst, config, n_frames=1, min_tiles=16):
+    """The noise profile of a burst (noise_profile.estimate_noise_profile) from its reference frame `ref_raw`, already
+    normalised, and with n_frames > 1 from the next n_frames - 1 frames of `raw_comp` as well (clamped to the burst's
+    length); integer frames are normalised as process() normalises the reference frame.  `mode: grey`: no CFA, unit gains."""
+    from .noise_profile import estimate_noise_profile
+    from .utils_dng import infer_width, normalize_burst, normalize_packed
+
+    frames = [ref_raw]
+    for i in range(max(1, min(int(n_frames), 1 + len(raw_comp))) - 1):
+        f = raw_comp[i]
+        if not torch.is_tensor(f) and np.issubdtype(np.asarray(f).dtype, np.integer):
+            norm = (burst["black_levels"], burst["white_level"], burst["white_balance"], burst["cfa_pattern"])
+            if burst.get("packing", None) is not None:
+                packing = np.asarray(burst["packing"]).item()
+                width = burst.get("width", None)
+                width = infer_width(np.asarray(f).shape[-1], packing) if width is None else int(np.asarray(width))
+                f = normalize_packed(np.asarray(f), width, packing, *norm)
+            else:
+                f = normalize_burst(np.asarray(f), *norm)
+        frames.append(f)
+    if config.mode == "grey":
+        return estimate_noise_profile(frames, None, None, min_tiles)
+    return estimate_noise_profile(frames, np.asarray(burst["cfa_pattern"]).tolist(),
+                                  [float(v) for v in list(burst["white_balance"])[:3]], min_tiles)
+
+
 def prepare_config(config, ref_raw, alpha=None, beta=None, cfa_pattern=None, white_balance=None, iso=100,
                    std_curve=None, diff_curve=None, shape=None):
     """The parameter derivation process() performs between loading the burst and calling main()
@@ -772,7 +798,17 @@ def process(burst_path, config):
     ``debug_dict["sharpness"]`` the candidates' scores (float64 ndarray).  The candidates are uploaded once for the score
     and again by main().  For a folder of .dng files the frame arrays are reordered; the tags (noise profile, ISO,
     orientation, colour matrix) stay those of file 0.  Another ``select`` or ``candidates`` < 1 is a ValueError before
-    anything is uploaded."""
+    anything is uploaded.
+    ``config.noise_model.source = "given" | "estimate"`` (optional; absent or "given": everything above, unchanged), with
+    ``noise_model.frames`` (default 1) and ``noise_model.min_tiles`` (default 16): with "estimate" the noise profile is
+    measured on the GPU (noise_profile.estimate_noise_profile: hhsr_noise_profile_hist, hhsr_noise_profile_fit) from the
+    normalised reference frame — after the reference selection — and with ``frames`` > 1 from the next frames as well
+    (clamped to the burst's length); the burst's own ``alpha`` / ``beta`` are ignored, the estimate feeds the curve
+    estimators and prepare_config() like a given pair (``config.noise_model.alpha`` / ``.beta`` hold it afterwards) and
+    ``debug_dict["noise profile"]`` is the estimator's dict (alpha, beta, per_colour, bins_used).  On a textured scene
+    the estimate is an upper bound (noise_profile.py).  A ``config.noise_model.alpha`` that is not None together with
+    "estimate", another ``source``, ``frames`` or ``min_tiles`` < 1 is a ValueError before anything is uploaded — so a
+    configuration object that went through an estimating call is reset (alpha: None) before the next."""
     import os
 
     from .utils_dng import infer_width, load_dng_burst, normalize_burst, normalize_packed
@@ -805,6 +841,9 @@ def process(burst_path, config):
         out_filter = png_option("filter", out_cfg.get("filter", "adaptive"))
         out_interval = png_option("interval_bytes", out_cfg.get("interval_bytes", None))
     ref_select, _ = reference_options(config)  # (refused now as well)
+    from .noise_profile import noise_options
+
+    noise_source, noise_frames, noise_min_tiles = noise_options(config)  # (and this)
     if isinstance(burst_path, (str, os.PathLike)) and str(burst_path).endswith(".npz"):
         burst = dict(np.load(burst_path))
     elif isinstance(burst_path, (str, os.PathLike)):
@@ -859,6 +898,10 @@ def process(burst_path, config):
         brightness_src = None
     std_curve, diff_curve = burst.get("std_curve"), burst.get("diff_curve")
     alpha, beta = burst.get("alpha"), burst.get("beta")
+    noise_profile = None
+    if noise_source == "estimate":  # the burst's own alpha / beta are ignored
+        noise_profile = estimate_burst_profile(ref_raw, raw_comp, burst, config, noise_frames, noise_min_tiles)
+        alpha, beta = noise_profile["alpha"], noise_profile["beta"]
     estimator = config.noise_model.get("estimator", "monte_carlo")
     if (std_curve is None or diff_curve is None) and estimator in ("monte_carlo", "monte_carlo_hip"):
         from .fast_monte_carlo import run_fast_MC  # the reference's estimator (super_resolution.py:252), seeded
@@ -875,6 +918,8 @@ def process(burst_path, config):
     if ref_index is not None:
         debug_dict["reference index"] = int(ref_index)
         debug_dict["sharpness"] = np.asarray(ref_scores, np.float64)
+    if noise_profile is not None:
+        debug_dict["noise profile"] = noise_profile
 
     # ---- after the path (reference super_resolution.py:303-356), on the device --------------------------------------
     from . import raw2rgb

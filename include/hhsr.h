@@ -499,6 +499,55 @@ int hhsr_sharpness_workspace(int H, int W, int n_frames, size_t* bytes);
 int hhsr_frame_sharpness(const void* const* frames, int n_frames, int H, int W, int64_t row_bytes, int format,
                          const uint8_t* cfa, void* workspace, size_t workspace_bytes, double* scores, void* stream);
 
+/* ---- noise profile: (alpha, beta) of a burst that brings none ---------------------------------------------------------------
+ * The reference reads the two numbers of its noise model, variance = alpha x + beta on normalised raw values, from the DNG
+ * NoiseProfile tag (super_resolution.py:232-238).  Arrays, .npz files, sensor counts and packed rows have no such tag: these
+ * two entry points estimate the pair from the frames.  No counterpart in the reference.  The estimator, stated once
+ * (tests/noise_profile_ref.py is its NumPy form):
+ *
+ *   frame     float32 [H][W], normalised and white-balanced (what main() receives), H and W even; h = H / 2, w = W / 2.
+ *   value     u = v * inv_gain[p], one float32 multiplication, p = (row & 1) * 2 + (col & 1) the CFA position; inv_gain[p] is
+ *             the float32 reciprocal of wb[cfa[p]] / wb[1] (all 1 for a monochrome sensor): the statistics are taken before
+ *             the white balance, like the DNG tag, and a saturated pixel sits at u = 1 whatever its colour.
+ *   tile      8 x 8 quads of ONE plane p (a 16 x 16 pixel block of the frame holds one tile of each plane), at multiples of 8
+ *             quads; quads right of 8 (w / 8) or below 8 (h / 8) belong to no tile and are not read; no halo.
+ *   counts    a tile counts if each of its 64 values satisfies 0 < u < 1 (NaN does not): no clipped or saturated tile.
+ *   mean      m = s / 64, s the float64 sum of the 64 values: each row's 8 values are added left to right, then the 8 row
+ *             sums top to bottom.
+ *   residual  at the 36 interior quads, r = u(y, x) - 0.25f * ((u(y, x-1) + u(y, x+1)) + (u(y-1, x) + u(y+1, x))) in float32,
+ *             not contracted.
+ *   energy    e = float32(S / 45.0), S the float64 sum of the float32 products r * r in the same order (6 per row left to
+ *             right, then the 6 row sums top to bottom); 45 = 36 x 1.25, the residual's variance gain for white noise.  A tile
+ *             with e == 0 is dropped.
+ *   bins      mean bin b = min(63, int(m * 64)); energy bin k = clamp((bits(e) >> 18) - ((127 - 32) << 5), 0, 1023), bits(e)
+ *             the float's bit pattern: 32 octaves below 1 at 32 bins each; below 2^-32: bin 0, 1 and above: bin 1023.
+ *   histogram uint32 [4 planes][64][1024] (1 MiB): one integer atomic add per tile, so the result does not depend on any order:
+ *             the same bits for any row stride, alignment, split of the frames into calls (added up) and frame order.
+ *
+ * hhsr_noise_profile_hist: frames HOST table of n_frames (1 .. HHSR_MAX_BATCH) DEVICE pointers, one shape; row y of frame n
+ *   starts at (char*)frames[n] + y * row_bytes.  cfa: HOST, 4 bytes, or NULL for a monochrome sensor (only checked here: the
+ *   planes are positions).  inv_gain: HOST float[4].  hist: DEVICE, 1 MiB, zeroed on `stream` by the call, then the tiles of
+ *   all frames of the call are added.  A frame smaller than one tile has none: the histogram stays zero, return 0.  Every byte
+ *   of a whole 16 x 16 block is read once, with 16-byte loads where frames[n] and row_bytes are multiples of 16 and dword loads
+ *   elsewhere; nothing else is read.  One memset node and one launch, no allocation, copy or synchronisation: capturable.
+ *   Error -1, before any HIP call: a null pointer (cfa excepted), n_frames outside 1 .. HHSR_MAX_BATCH, H or W odd or <= 0,
+ *   H > 16 * 65535 + 15 (the grid), W > INT32_MAX / 4, row_bytes < 4 W or not a multiple of 4, H row_bytes beyond int64, a
+ *   frame pointer or hist off 4 bytes, a cfa entry above 2.
+ * hhsr_noise_profile_fit (host only, no HIP call): hist HOST [4][64][1024].  Per colour c (R, G, B) the planes with
+ *   cfa[p] == c are added (green: its two); cfa NULL: all four, one pair, written to all three.  Per mean bin with n_b >=
+ *   min_tiles (>= 1; 16 is a good default) tiles: x_b = (b + 0.5) / 64, y_b = the median of the bin's energy histogram: at the
+ *   first k whose cumulative count reaches 0.5 n_b, interpolated linearly between the bin's edges, the floats with the bits
+ *   (k + ((127 - 32) << 5)) << 18 and that plus 1 << 18: y_b = lo + (0.5 n_b - count below k) / count[k] * (hi - lo).
+ *   y = alpha x + beta by least squares in float64 with the weights n_b / y_b^2; a negative intercept is refitted with
+ *   beta = 0, otherwise a negative slope with alpha = 0.  alpha_beta: HOST double[8] = (alpha, beta) of R, G, B and their mean
+ *   (the reference's rule for the three pairs of the DNG tag, super_resolution.py:236-238); bins_used: HOST int[3], the usable
+ *   bins per colour, written in every case.  Error -3: a colour with fewer than 2 usable bins (hhsr_last_error names the first).
+ *   Known bias, not corrected: the median of a tile energy lies 1 - 2 % below the variance, and texture finer than a tile
+ *   counts as noise: on a textured scene the result is an upper bound. */
+int hhsr_noise_profile_hist(const void* const* frames, int n_frames, int H, int W, int64_t row_bytes, const uint8_t* cfa,
+                            const float* inv_gain, uint32_t* hist, void* stream);
+int hhsr_noise_profile_fit(const uint32_t* hist, const uint8_t* cfa, int min_tiles, double* alpha_beta, int* bins_used);
+
 /* ---- after the path: frame-count denoisers, postprocess, orientation — on the device -------------
  * hhsr_frame_count_denoise: utils_image.py:174-309.  image / out float32 [H][W][3] (the merged image), acc_r float32
  * [ah][aw] (accumulated robustness).  kind 0 = median (strength_max = radius_max <= 7: the reference's 16 x 16 sample
