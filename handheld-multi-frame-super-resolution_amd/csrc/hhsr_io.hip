@@ -8,6 +8,8 @@
 // per pixel: HBM bound; each thread converts 8 pixels of one row (one 16-byte load, two 16-byte stores).
 #include "hhsr_common.h"
 
+#include <math.h>
+
 struct NormArgs {
     float black[4], inv_unused, den[4], gain[4];  // per position of the 2x2 CFA cell: (row & 1) * 2 + (col & 1)
 };
@@ -507,6 +509,276 @@ extern "C" int hhsr_frame_sharpness(const void* const* frames, int n_frames, int
 #undef HHSR_SHARP
     hipLaunchKernelGGL(k_sharpness_sum, dim3(n_frames), dim3(HHSR_WAVE), 0, s, (const double*)part, (int)tiles, scores);
     HHSR_LAUNCHED();
+}
+
+// ---- white balance of a burst that brings none (include/hhsr.h: "white balance") -------------------------------------------
+// The statistic on the device (hhsr_white_balance_hist), the fit on the host (hhsr_white_balance_fit).  No counterpart in
+// the reference, which takes rawpy's camera_whitebalance.  One pass over the counts as they lie in memory, every byte of
+// every whole 16 x 16 pixel tile read once, nothing else read:
+//   thread     one quad row of one tile: pixel rows 2 y and 2 y + 1, 16 pixels each — per row one packed chunk (read_chunk,
+//              dwords) or 32 bytes of uint16 (two 16-byte loads where the frame and its row stride are multiples of 16 bytes,
+//              count by count elsewhere: the same values).  It adds its 8 counts of each CFA position in integers and notes
+//              whether one of them reaches the position's saturation count.
+//   8 lanes    one tile, lane y its quad row y: the four integer sums go through three xor shuffles, the saturation flags
+//              through one ballot.  Every lane then holds the tile's sums and forms the two bins; lane 0 of the 8 owns them.
+//   wave       8 tiles side by side: 256 contiguous bytes of uint16 per row.
+//   workgroup  4 waves side by side, WB_ROWS = 2 tile rows below each other: WB_GROUP_TILES = 64 tiles, 512 x 32 pixels;
+//              grid (ceil(tiles / 32), ceil(tile rows / 2), frames).  The tiles' bins meet in LDS, equal bins are merged and
+//              the first tile of each bin adds their number with ONE vector integer atomic.
+// Everything up to the two float32 quotients is integer; the float32 steps are the single operations of hhsr.h, not
+// contracted (build.py), so the histogram is a function of the counts alone.
+//
+// The atomics decided the form.  An atomic add to an address that others add to completes about every 12 ns on this chip
+// (measured below: 46750 adds to one address in 536 us), and a frame puts most tiles into few bins.  12 MP, per frame,
+// (textured synthetic frame | uniform grey frame: every tile in ONE bin), one frame per call / eight, uint16:
+//   one atomic per tile                     38.6 | 536    us  /  32.1 | 531   us
+//   equal bins merged per wave (8 tiles)    36.8 |  74.6      /  29.8 |  69.1
+//   merged per workgroup of 32 tiles        22.3 |  24.0      /  16.4 |  18.3
+//   merged per workgroup, 2 tile rows       17.4 |  17.1      /  10.3 |  10.4    <- kept (loads of both rows in flight)
+//   4 tile rows                             22.1 |  18.0      /  10.8 |   7.4
+//   8 tile rows                             26.2 |  21.7      /  10.9 |   6.6
+// hhsr_frame_sharpness on the same frames: 15.4 - 15.9 / 5.3 us (profiles/white_balance.txt holds every row; mipi10 rows
+// give the same picture).
+// More rows per workgroup help only the uniform frame in calls of eight and cost the single-frame call, which is what
+// process() makes, its parallelism: 94 x 8 workgroups of 2 rows against 24 x 8 of 8.
+#define WB_WAVES 4
+#define WB_WAVE_TILES 8
+#define WB_SPAN_TILES (WB_WAVES * WB_WAVE_TILES)
+#define WB_ROWS 2
+#define WB_GROUP_TILES (WB_SPAN_TILES * WB_ROWS)
+#define WB_BIN_BASE ((127 - 2) << 5)  // (exponent, 5 mantissa bits) of 2^-2: bin 0
+#define WB_HIST_BYTES ((size_t)HHSR_WB_BINS * HHSR_WB_BINS * sizeof(uint32_t))
+
+struct WbArgs {
+    const uint8_t* p[HHSR_MAX_BATCH];
+    int sat[4];                 // per CFA position: a count >= sat drops the tile
+    int colour[4];              // per CFA position: 0 R, 1 G, 2 B
+    float black[3], den[3];     // per colour: the casts of hhsr_normalize_raw_u16
+};
+
+// the 16 counts of tile column bx of the row at `row`.  FAST: the caller has checked that every row starts on 16 bytes
+// (packed: on a dword) — vector loads with no branch around them; otherwise count by count (packed: read_chunk decides).
+template <int FMT, bool FAST>
+__device__ __forceinline__ void wb_load(const uint8_t* __restrict__ row, int bx, uint32_t (&p)[16]) {
+    if constexpr (FMT == SHARP_FMT_U16) {
+        const uint16_t* __restrict__ src = reinterpret_cast<const uint16_t*>(row) + (size_t)bx * 16;
+        if constexpr (FAST) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const uint4 q = reinterpret_cast<const uint4*>(src)[j];
+                const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    p[8 * j + 2 * k] = w[k] & 0xffffu;
+                    p[8 * j + 2 * k + 1] = w[k] >> 16;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) p[k] = src[k];
+        }
+    } else {
+        constexpr int BITS = 10 + 2 * ((FMT - 1) % 3);
+        constexpr bool BE = FMT >= HHSR_PACK_BE10;
+        if constexpr (FAST)
+            read_chunk_whole<BITS, BE>(row + (size_t)bx * (2 * BITS), p);
+        else
+            read_chunk<BITS, BE>(row + (size_t)bx * (2 * BITS), 16, p);
+    }
+}
+
+// bin u * 192 + v of tile (ty, bx), or -1 for a tile that is dropped or, with `live` false, not there: (ty, bx) is then any
+// tile that exists, read from cache and thrown away, so that the loads have no branch around them and those of a
+// workgroup's WB_ROWS tile rows can all be in flight at once.  Valid in all 8 lanes of the tile; all 64 lanes of the wave
+// call it (the shuffles).
+template <int FMT, bool FAST>
+__device__ __forceinline__ int wb_tile_bin(const WbArgs& A, const uint8_t* __restrict__ frame, size_t row_bytes, int ty, int bx,
+                                           bool live, int g, int y) {
+    const uint8_t* __restrict__ top = frame + ((size_t)ty * 16 + 2 * y) * row_bytes;
+    uint32_t t[16], b[16];
+    wb_load<FMT, FAST>(top, bx, t);
+    wb_load<FMT, FAST>(top + row_bytes, bx, b);
+    int s[4] = {0, 0, 0, 0};
+    uint32_t mx[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        s[0] += (int)t[2 * k], s[1] += (int)t[2 * k + 1], s[2] += (int)b[2 * k], s[3] += (int)b[2 * k + 1];
+        mx[0] = max(mx[0], t[2 * k]), mx[1] = max(mx[1], t[2 * k + 1]);
+        mx[2] = max(mx[2], b[2 * k]), mx[3] = max(mx[3], b[2 * k + 1]);
+    }
+    bool clipped = false;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) clipped = clipped || (int)mx[q] >= A.sat[q];
+#pragma unroll
+    for (int o = 1; o < 8; o <<= 1) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s[q] += __shfl_xor(s[q], o, HHSR_WAVE);
+    }
+    const bool tile_clipped = ((__ballot(clipped) >> (g * 8)) & 0xffull) != 0;
+    int S[3] = {0, 0, 0};  // per colour: 64 counts of R and B, 128 of G, < 2^24
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) S[c] += A.colour[q] == c ? s[q] : 0;
+    }
+    const float mr = ((float)S[0] / 64.0f - A.black[0]) / A.den[0];
+    const float mg = ((float)S[1] / 128.0f - A.black[1]) / A.den[1];
+    const float mb = ((float)S[2] / 64.0f - A.black[2]) / A.den[2];
+    const float lo = 1.0f / 64.0f;
+    if (live && !tile_clipped && mr >= lo && mg >= lo && mb >= lo) {  // (NaN fails)
+        const int u = (int)(__float_as_uint(mg / mr) >> 18) - WB_BIN_BASE;
+        const int v = (int)(__float_as_uint(mg / mb) >> 18) - WB_BIN_BASE;
+        if (u >= 0 && u < HHSR_WB_BINS && v >= 0 && v < HHSR_WB_BINS) return u * HHSR_WB_BINS + v;
+    }
+    return -1;
+}
+
+// the bins of the workgroup's tiles -> sb[tile row][tile column]
+template <int FMT, bool FAST>
+__device__ __forceinline__ void wb_rows(const WbArgs& A, const uint8_t* __restrict__ frame, size_t row_bytes, int nbx, int nby,
+                                        int* __restrict__ sb) {
+    const int lane = threadIdx.x & (HHSR_WAVE - 1), wv = threadIdx.x / HHSR_WAVE;
+    const int g = lane >> 3, y = lane & 7;
+    const int bx = (blockIdx.x * WB_WAVES + wv) * WB_WAVE_TILES + g;
+    constexpr int rows = WB_ROWS, unrolled = FAST ? rows : 1;  // (the slow path is long code: kept rolled)
+#pragma unroll unrolled
+    for (int r = 0; r < rows; ++r) {
+        const int ty = blockIdx.y * WB_ROWS + r;  // (uniform)
+        const bool live = bx < nbx && ty < nby;   // (the same in the 8 lanes of a tile)
+        const int bin = wb_tile_bin<FMT, FAST>(A, frame, row_bytes, min(ty, nby - 1), min(bx, nbx - 1), live, g, y);
+        if (y == 0) sb[r * WB_SPAN_TILES + wv * WB_WAVE_TILES + g] = bin;
+    }
+}
+
+template <int FMT>
+__global__ void __launch_bounds__(WB_WAVES* HHSR_WAVE) k_white_balance(WbArgs A, int nbx, int nby, size_t row_bytes,
+                                                                        uint32_t* __restrict__ hist) {
+    __shared__ __attribute__((aligned(16))) int sb[WB_GROUP_TILES];
+    const uint8_t* __restrict__ frame = A.p[blockIdx.z];
+    constexpr uintptr_t align = FMT > 0 ? 3 : 15;
+    if (((((uintptr_t)frame) | row_bytes) & align) == 0)  // (uniform per frame)
+        wb_rows<FMT, true>(A, frame, row_bytes, nbx, nby, sb);
+    else
+        wb_rows<FMT, false>(A, frame, row_bytes, nbx, nby, sb);
+    __syncthreads();
+    // equal bins among the workgroup's tiles: the first of them adds their number
+    for (int e = threadIdx.x; e < WB_GROUP_TILES; e += WB_WAVES * HHSR_WAVE) {
+        const int mine = sb[e];
+        unsigned cnt = 0;
+        bool first = true;
+        for (int j = 0; j < WB_GROUP_TILES; j += 4) {
+            const int4 q = *reinterpret_cast<const int4*>(sb + j);  // (the same address in every lane: a broadcast)
+            const int bj[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                cnt += bj[k] == mine;
+                first = first && !(j + k < e && bj[k] == mine);
+            }
+        }
+        if (mine >= 0 && first) atomicAdd(hist + mine, cnt);
+    }
+}
+
+extern "C" int hhsr_white_balance_hist(const void* const* frames, int n_frames, int H, int W, int64_t row_bytes, int format,
+                                       const uint8_t cfa[4], const double* black_levels, double white_level, uint32_t* hist,
+                                       void* stream) {
+    HHSR_ARG(frames && cfa && black_levels && hist);
+    HHSR_ARG(n_frames >= 1 && n_frames <= HHSR_MAX_BATCH);
+    int tx, ty;
+    HHSR_ARG(sharp_tiles(H, W, &tx, &ty) > 0);  // the limits of hhsr_frame_sharpness: H, W even and > 0, 32-bit indices
+    HHSR_ARG(H / 16 <= 65535);                  // the grid's y size
+    HHSR_ARG(format == SHARP_FMT_U16 || (format >= HHSR_PACK_MIPI10 && format <= HHSR_PACK_BE14));
+    int count[3] = {0, 0, 0};
+    for (int k = 0; k < 4; ++k) {
+        HHSR_ARG(cfa[k] <= 2);
+        ++count[cfa[k]];
+    }
+    HHSR_ARG(count[0] == 1 && count[1] == 2 && count[2] == 1);
+    const int item = format == SHARP_FMT_U16 ? 2 : 1;
+    const int64_t need = format > 0 ? packed_row_bytes(W, format) : (int64_t)item * W;
+    HHSR_ARG(row_bytes >= need && row_bytes % item == 0);
+    HHSR_ARG(row_bytes <= INT64_MAX / H);  // the byte offset of the last row
+    for (int n = 0; n < n_frames; ++n) HHSR_ARG(frames[n] != nullptr && ((uintptr_t)frames[n] & (item - 1)) == 0);
+    HHSR_ARG(((uintptr_t)hist & 3) == 0);
+    WbArgs A;
+    for (int c = 0; c < 3; ++c) {
+        HHSR_ARG(white_level > black_levels[c]);
+        A.black[c] = (float)black_levels[c];  // the casts of hhsr_normalize_raw_u16
+        A.den[c] = (float)(white_level - black_levels[c]);
+    }
+    for (int k = 0; k < 4; ++k) {
+        const int c = cfa[k];
+        const double sat = ceil(black_levels[c] + 15.0 / 16.0 * (white_level - black_levels[c]));
+        A.colour[k] = c;
+        A.sat[k] = sat >= 65536.0 ? 65536 : (sat > 0.0 ? (int)sat : 0);  // (a count is at most 65535; NaN: 0, every tile dropped)
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const hipError_t e = hipMemsetAsync(hist, 0, WB_HIST_BYTES, s);
+    if (e != hipSuccess) {
+        hhsr_set_error("%s: hipMemsetAsync failed: %s", __func__, hipGetErrorString(e));
+        return (int)e;
+    }
+    const int nbx = W / 16, nby = H / 16;
+    if (nbx == 0 || nby == 0) return 0;  // a frame smaller than one tile has none
+    for (int n = 0; n < HHSR_MAX_BATCH; ++n) A.p[n] = (const uint8_t*)frames[n < n_frames ? n : 0];
+    const dim3 grid((nbx + WB_SPAN_TILES - 1) / WB_SPAN_TILES, (nby + WB_ROWS - 1) / WB_ROWS, n_frames);
+#define HHSR_WB(ID)                                                                                                   \
+    case ID:                                                                                                          \
+        hipLaunchKernelGGL((k_white_balance<ID>), grid, dim3(WB_WAVES* HHSR_WAVE), 0, s, A, nbx, nby, (size_t)row_bytes, hist); \
+        break;
+    switch (format) {
+        HHSR_WB(SHARP_FMT_U16)
+        HHSR_WB(HHSR_PACK_MIPI10)
+        HHSR_WB(HHSR_PACK_MIPI12)
+        HHSR_WB(HHSR_PACK_MIPI14)
+        HHSR_WB(HHSR_PACK_BE10)
+        HHSR_WB(HHSR_PACK_BE12)
+        HHSR_WB(HHSR_PACK_BE14)
+    }
+#undef HHSR_WB
+    HHSR_LAUNCHED();
+}
+
+// the fit (host only): centre of bin k in log2 units
+static double wb_centre(int k) { return log2(ldexp(1.0 + ((k & 31) + 0.5) / 32.0, (k >> 5) - 2)); }
+
+extern "C" int hhsr_white_balance_fit(const uint32_t* hist, int min_tiles, double white_balance[3], int64_t tiles[2]) {
+    HHSR_ARG(hist && white_balance && tiles);
+    HHSR_ARG(min_tiles >= 1);
+    double centre[HHSR_WB_BINS];
+    for (int k = 0; k < HHSR_WB_BINS; ++k) centre[k] = wb_centre(k);
+    // the count-weighted centroid of the bins within `radius` of (cu, cv) (radius < 0: of all bins), rows then columns
+    auto centroid = [&](double cu, double cv, double radius, double* ou, double* ov) {
+        double su = 0.0, sv = 0.0;
+        int64_t n = 0;
+        for (int u = 0; u < HHSR_WB_BINS; ++u)
+            for (int v = 0; v < HHSR_WB_BINS; ++v) {
+                const uint32_t c = hist[u * HHSR_WB_BINS + v];
+                if (c == 0) continue;
+                if (radius >= 0.0) {
+                    const double du = centre[u] - cu, dv = centre[v] - cv;
+                    if (!(du * du + dv * dv <= radius * radius)) continue;
+                }
+                su += (double)c * centre[u], sv += (double)c * centre[v], n += c;
+            }
+        if (n > 0) *ou = su / (double)n, *ov = sv / (double)n;
+        return n;
+    };
+    double u = 0.0, v = 0.0;
+    const int64_t N = centroid(0.0, 0.0, -1.0, &u, &v);
+    tiles[0] = N, tiles[1] = 0;
+    white_balance[0] = white_balance[1] = white_balance[2] = 1.0;
+    if (N < min_tiles) {
+        hhsr_set_error("%s: %lld usable tiles, fewer than min_tiles = %d", __func__, (long long)N, min_tiles);
+        return -3;
+    }
+    for (int it = 0; it < 4; ++it) {
+        const int64_t n = centroid(u, v, 0.5, &u, &v);
+        tiles[1] = n;
+        if (n == 0) break;  // an empty gate: the estimate stays
+    }
+    white_balance[0] = exp2(u), white_balance[2] = exp2(v);
+    return 0;
 }
 
 // ---- shader-clock probe (measurement support: bench.py's "sclk_mhz") --------------------------------------------

@@ -7,5 +7,7 @@ GPU; calling into the hot path without one (or without the built library) raises
 from .config import Config, OmegaConf, default_config  # noqa: F401
 from .super_resolution import process, main, prepare_config, BurstPipeline, select_reference  # noqa: F401
 from .noise_profile import estimate_noise_profile  # noqa: F401
+from .white_balance import estimate_white_balance  # noqa: F401
 
-__all__ = ["process", "main", "prepare_config", "BurstPipeline", "select_reference", "estimate_noise_profile", "Config", "OmegaConf", "default_config"]
+__all__ = ["process", "main", "prepare_config", "BurstPipeline", "select_reference", "estimate_noise_profile",
+           "estimate_white_balance", "Config", "OmegaConf", "default_config"]

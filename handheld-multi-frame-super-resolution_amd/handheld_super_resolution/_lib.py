@@ -55,6 +55,8 @@ _SIGS = {
     "hhsr_frame_sharpness": [PP, I, I, I, L, I, U8P, P, SZ, P, P],
     "hhsr_noise_profile_hist": [PP, I, I, I, L, U8P, FP, P, P],
     "hhsr_noise_profile_fit": [P, U8P, I, DP, I32P],
+    "hhsr_white_balance_hist": [PP, I, I, I, L, I, U8P, DP, D, P, P],
+    "hhsr_white_balance_fit": [P, I, DP, I64P],
     "hhsr_rob_upscale": [P, I, I, P, I, I, I, P, P],
     "hhsr_rob_s": [P, I, I, D, F, F, P, I, I, P],
     "hhsr_rob_sigma": [P, P, I, I, P, I, P, P, P],

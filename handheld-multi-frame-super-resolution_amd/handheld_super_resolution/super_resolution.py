@@ -712,6 +712,23 @@ def estimate_burst_profile(ref_raw, raw_comp, burst, config, n_frames=1, min_til
                                   [float(v) for v in list(burst["white_balance"])[:3]], min_tiles)
 
 
+def estimate_burst_white_balance(ref_raw, raw_comp, burst, n_frames=1, min_tiles=16):
+    """The white balance of a burst of integer counts (white_balance.estimate_white_balance) from its reference frame
+    `ref_raw` and, with n_frames > 1, from the next n_frames - 1 frames of `raw_comp` as well (clamped to the burst's
+    length): uint16 counts or, with burst["packing"], packed rows, uploaded and measured as they are."""
+    from .utils_dng import infer_width
+    from .white_balance import estimate_white_balance
+
+    frames = [ref_raw] + [raw_comp[i] for i in range(max(1, min(int(n_frames), 1 + len(raw_comp))) - 1)]
+    packing = width = None
+    if burst.get("packing", None) is not None:
+        packing = np.asarray(burst["packing"]).item()
+        width = burst.get("width", None)
+        width = infer_width(np.asarray(ref_raw).shape[-1], packing) if width is None else int(np.asarray(width))
+    return estimate_white_balance(frames, np.asarray(burst["cfa_pattern"]).tolist(), burst["black_levels"],
+                                  float(burst["white_level"]), packing, width, min_tiles)
+
+
 def prepare_config(config, ref_raw, alpha=None, beta=None, cfa_pattern=None, white_balance=None, iso=100,
                    std_curve=None, diff_curve=None, shape=None):
     """The parameter derivation process() performs between loading the burst and calling main()
@@ -808,7 +825,19 @@ def process(burst_path, config):
     ``debug_dict["noise profile"]`` is the estimator's dict (alpha, beta, per_colour, bins_used).  On a textured scene
     the estimate is an upper bound (noise_profile.py).  A ``config.noise_model.alpha`` that is not None together with
     "estimate", another ``source``, ``frames`` or ``min_tiles`` < 1 is a ValueError before anything is uploaded — so a
-    configuration object that went through an estimating call is reset (alpha: None) before the next."""
+    configuration object that went through an estimating call is reset (alpha: None) before the next.
+    ``config.white_balance = {"source": "given" | "estimate", "frames": 1, "min_tiles": 16}`` (optional; absent or "given":
+    the burst's ``white_balance``, and nothing below runs): with "estimate" a Bayer burst of integer counts needs no
+    ``white_balance`` key — the gains are measured on the GPU (white_balance.estimate_white_balance:
+    hhsr_white_balance_hist, hhsr_white_balance_fit) from the reference frame's counts, after the reference selection and
+    before anything is normalised, with ``frames`` > 1 from the next frames' counts as well (clamped to the burst's length).
+    The burst's own ``white_balance`` is ignored; the estimate is what the normalisation of every frame, the noise
+    estimate and prepare_config() / ``config.exif`` see, and ``debug_dict["white balance"]`` is the estimator's dict
+    (white_balance, tiles, tiles_gated).  It is a grey-world estimate: a scene whose balanced channel means differ is
+    estimated wrong by that difference.  ``mode: grey``, frames that are not integer counts (float frames are already
+    balanced; a folder of .dng files comes back normalised), another ``source``, ``frames`` or ``min_tiles`` < 1 is a
+    ValueError before anything is uploaded; fewer than ``min_tiles`` usable tiles is the ValueError of
+    fit_white_balance."""
     import os
 
     from .utils_dng import infer_width, load_dng_burst, normalize_burst, normalize_packed
@@ -844,6 +873,15 @@ def process(burst_path, config):
     from .noise_profile import noise_options
 
     noise_source, noise_frames, noise_min_tiles = noise_options(config)  # (and this)
+    from .white_balance import wb_options
+
+    wb_source, wb_frames, wb_min_tiles = wb_options(config)  # (and this)
+    if wb_source == "estimate":
+        if config.mode == "grey":
+            raise ValueError("config.white_balance.source 'estimate' with mode grey: a monochrome sensor has no white balance")
+        if isinstance(burst_path, (str, os.PathLike)) and not str(burst_path).endswith(".npz"):
+            raise ValueError("config.white_balance.source 'estimate' needs integer sensor counts: a folder of .dng files "
+                             "comes back normalised and balanced by its own AsShotNeutral")
     if isinstance(burst_path, (str, os.PathLike)) and str(burst_path).endswith(".npz"):
         burst = dict(np.load(burst_path))
     elif isinstance(burst_path, (str, os.PathLike)):
@@ -866,11 +904,18 @@ def process(burst_path, config):
         burst.setdefault("cfa_pattern", [[0, 1], [1, 2]])
         burst.setdefault("white_balance", [1.0, 1.0, 1.0])
     ref_raw, raw_comp = burst["ref"], burst["comp"]
+    if wb_source == "estimate" and (torch.is_tensor(ref_raw) or not np.issubdtype(np.asarray(ref_raw).dtype, np.integer)):
+        raise ValueError("config.white_balance.source 'estimate' needs integer sensor counts (with black_levels and "
+                         "white_level): float frames are taken as normalised and already white-balanced")
     ref_index = ref_scores = None
     if ref_select == "sharpest":  # the chosen frame is `ref` from here on
         ref_index, ref_scores = select_reference(ref_raw, raw_comp, config, burst["cfa_pattern"], burst.get("packing", None),
                                                  burst.get("width", None))
         ref_raw, raw_comp = reorder_burst(ref_raw, raw_comp, ref_index)
+    wb_estimate = None
+    if wb_source == "estimate":  # the burst's own white_balance is ignored
+        wb_estimate = estimate_burst_white_balance(ref_raw, raw_comp, burst, wb_frames, wb_min_tiles)
+        burst = dict(burst, white_balance=wb_estimate["white_balance"])
     if not torch.is_tensor(ref_raw) and np.issubdtype(np.asarray(ref_raw).dtype, np.integer):
         # sensor counts + metadata: the normalisation / white balance of utils_dng.py:149-160, on the GPU.  The
         # reference frame now (its brightness picks the SNR-based parameters); the other frames stay integer host arrays
@@ -920,6 +965,8 @@ def process(burst_path, config):
         debug_dict["sharpness"] = np.asarray(ref_scores, np.float64)
     if noise_profile is not None:
         debug_dict["noise profile"] = noise_profile
+    if wb_estimate is not None:
+        debug_dict["white balance"] = wb_estimate
 
     # ---- after the path (reference super_resolution.py:303-356), on the device --------------------------------------
     from . import raw2rgb

@@ -6,7 +6,10 @@
 --outpath  .png: 8-bit PNG;  .tif / .tiff: 16-bit uncompressed TIFF (post-processing as configured);  .dng: not built —
            the reference's DNG export runs exiftool and dng_validate on such a TIFF
 --config   a YAML file merged over the defaults (config.DEFAULTS)
-key=value  overrides, e.g. scale=2 robustness.save_mask=false; the values are read as YAML scalars, never evaluated
+key=value  overrides, e.g. scale=2 robustness.save_mask=false; the values are read as YAML scalars, never evaluated.  The
+           optional sections of process() are reached the same way: reference.select=sharpest, noise_model.source=estimate,
+           white_balance.source=estimate (white_balance.frames=2 white_balance.min_tiles=8) for a burst of integer counts
+           that brings no white_balance
 
 The image is quantised on the GPU (config.output.dtype, hhsr_encode_image) and written with the standard library
 (utils_image.save_png, utils_dng.save_as_tiff).  With the override output.format=png and a .png outpath the PNG itself is

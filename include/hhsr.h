@@ -548,6 +548,58 @@ int hhsr_noise_profile_hist(const void* const* frames, int n_frames, int H, int 
                             const float* inv_gain, uint32_t* hist, void* stream);
 int hhsr_noise_profile_fit(const uint32_t* hist, const uint8_t* cfa, int min_tiles, double* alpha_beta, int* bins_used);
 
+/* ---- white balance: gains of a burst that brings none ----------------------------------------------------------------------
+ * The reference multiplies rawpy's camera_whitebalance (DNG AsShotNeutral) into every frame (utils_dng.py:149-160).  Counts
+ * that come from a sensor interface have no such tag: these two entry points estimate the gains (R, 1, B) from the counts,
+ * the black and white levels and the CFA pattern.  No counterpart in the reference.  The estimator, stated once
+ * (tests/white_balance_ref.py is its NumPy form); every step is exact integer arithmetic or ONE correctly rounded float32
+ * operation, not contracted:
+ *
+ *   frame     counts [H][W], uint16 or packed rows (the layouts of hhsr_normalize_raw_packed), H and W even, NOT normalised.
+ *   tile      the whole 16 x 16 pixel blocks at (16 i, 16 j); rows and columns behind the last whole tile are not read.
+ *   sums      per colour c, S_c = the integer sum of the tile's counts at the CFA positions of colour c; n_c = 64 for R and
+ *             B, 128 for G (S_c <= 128 x 65535 < 2^24: float32(S_c) is exact).
+ *   clipping  a tile is dropped if any of its counts is >= sat_c of its colour, sat_c = ceil(black_c + 15 / 16 (white -
+ *             black_c)) in float64: a clipped channel fakes a chroma.
+ *   means     m_c = (float32(S_c) / float32(n_c) - float32(black_c)) / float32(white - black_c), the casts of
+ *             hhsr_normalize_raw_u16.  A tile is dropped unless every m_c >= 1 / 64 (which removes non-positive means).
+ *   chroma    q_r = m_G / m_R, q_b = m_G / m_B: the gains that would make this tile grey.
+ *   bins      u = (bits(q_r) >> 18) - ((127 - 2) << 5), v the same of q_b, bits(q) the float's bit pattern: 32 bins per
+ *             octave from 1 / 4 on.  A tile is dropped unless 0 <= u, v < HHSR_WB_BINS: gains in [1 / 4, 16).
+ *   histogram uint32 [192][192] (144 KiB), hist[u][v] += 1: integer adds, so the result does not depend on any order: the same
+ *             bits for any row stride, alignment, format of the same counts, split of the frames into calls (added up) and
+ *             frame order.
+ *
+ * hhsr_white_balance_hist: frames HOST table of n_frames (1 .. HHSR_MAX_BATCH) DEVICE pointers, one shape and format; row y
+ *   of frame n starts at (char*)frames[n] + y * row_bytes.  format: -1 uint16 or HHSR_PACK_*, as for hhsr_frame_sharpness;
+ *   0 (float32) is refused: normalised float frames are already white-balanced by this library's convention.  cfa: HOST,
+ *   4 bytes, required (a monochrome sensor has no white balance), one entry 0, two 1, one 2.  black_levels: HOST double[3]
+ *   by colour.  hist: DEVICE, zeroed on `stream` by the call, then the tiles of all frames of the call are added.  A frame
+ *   smaller than one tile has none: the histogram stays zero, return 0.  Every byte of a whole tile is read once — uint16
+ *   with 16-byte loads where frames[n] and row_bytes are multiples of 16 and count by count elsewhere, packed rows by the
+ *   reader of hhsr_normalize_raw_packed (dwords where the row starts on one, bytes elsewhere) — and nothing else is read.
+ *   One memset node and one launch, no allocation, copy or synchronisation: capturable.
+ *   Error -1, before any HIP call: a null pointer, n_frames outside 1 .. HHSR_MAX_BATCH, the sizes hhsr_frame_sharpness
+ *   refuses (H or W odd or <= 0, W > INT32_MAX - 2048), H > 16 * 65535 + 15 (the grid), format 0 or unknown, a cfa that is
+ *   not one R, two G and one B, row_bytes below the row's bytes (2 W, hhsr_packed_row_bytes) or odd for uint16, H row_bytes
+ *   beyond int64, a uint16 frame pointer off 2 bytes, hist off 4 bytes, white_level <= black_levels[c].
+ * hhsr_white_balance_fit (host only, no HIP call): hist HOST [192][192].  In float64, bins visited in the order (u, v), on the
+ *   bin centres c_k = log2(2^(k / 32 - 2, floored) (1 + ((k mod 32) + 0.5) / 32)):
+ *   1. N = the sum of all counts; N < min_tiles (>= 1; 16 is a good default): error -3 (the frame is too small, black or
+ *      clipped), white_balance = (1, 1, 1), tiles = (N, 0).
+ *   2. (cu, cv) = the count-weighted centroid of all bins' centres: a geometric grey world.
+ *   3. four times: (cu, cv) = the centroid of the bins whose centre (c_u, c_v) has (c_u - cu)^2 + (c_v - cv)^2 <= 0.25 —
+ *      within half an octave, which throws out a large coloured object; a gate that holds no tile ends the loop and the
+ *      estimate stays.
+ *   4. white_balance: HOST double[3] = (2^cu, 1, 2^cv); tiles: HOST int64[2] = (N, the tiles inside the last gate; 0 if it was
+ *      empty).
+ *   Grey world's own assumption — the scene's balanced channel means are equal — is not checked and cannot be. */
+#define HHSR_WB_BINS 192
+int hhsr_white_balance_hist(const void* const* frames, int n_frames, int H, int W, int64_t row_bytes, int format,
+                            const uint8_t cfa[4], const double* black_levels, double white_level, uint32_t* hist,
+                            void* stream);
+int hhsr_white_balance_fit(const uint32_t* hist, int min_tiles, double white_balance[3], int64_t tiles[2]);
+
 /* ---- after the path: frame-count denoisers, postprocess, orientation — on the device -------------
  * hhsr_frame_count_denoise: utils_image.py:174-309.  image / out float32 [H][W][3] (the merged image), acc_r float32
  * [ah][aw] (accumulated robustness).  kind 0 = median (strength_max = radius_max <= 7: the reference's 16 x 16 sample
