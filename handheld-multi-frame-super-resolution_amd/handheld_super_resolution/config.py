@@ -17,6 +17,8 @@ from __future__ import annotations
 import copy
 from typing import Any, Mapping
 
+import numpy as np
+
 __all__ = ["Config", "OmegaConf", "DEFAULTS", "default_config", "HIP_KNOBS", "hip_opt"]
 
 
@@ -263,3 +265,20 @@ def hip_opt(config, name):
     hip = config.get("hip", None) if hasattr(config, "get") else None
     return default if hip is None else hip.get(name, default)
 
+
+
+def estimate_options(section, sec, min_tiles):
+    """(source, frames, min_tiles) of a section with the keys source = "given" | "estimate" (absent: "given"), frames
+    (default 1) and min_tiles (default `min_tiles`); ValueError for anything else."""
+    source = str(sec.get("source", "given"))
+    if source not in ("given", "estimate"):
+        raise ValueError(f"config.{section}.source {source!r}: given or estimate")
+    return (source, positive_int(section, "frames", sec.get("frames", 1)),
+            positive_int(section, "min_tiles", sec.get("min_tiles", min_tiles)))
+
+
+def positive_int(section, key, value):
+    """`value` of config.SECTION.KEY as an int; ValueError unless it is a whole number of at least 1 (a bool is not)."""
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < 1:
+        raise ValueError(f"config.{section}.{key} {value!r}: an integer >= 1")
+    return int(value)

@@ -294,7 +294,7 @@ class HostBurstRunner:
     # ---- capture --------------------------------------------------------------------------------------------------
     def _capture(self, frames):
         from .super_resolution import BurstPipeline, _Staged, _stream_pool
-        from .utils_dng import packed_width
+        from .raw_frames import RawLayout
 
         cfg, dev = self.config, self.device
         n = len(frames) - 1
@@ -303,7 +303,7 @@ class HostBurstRunner:
         with torch.cuda.device(dev):
             st.stage = torch.empty((n + 1, H, W), dtype=frames[0].dtype, device=dev)
             # packed frames (raw_norm["packing"]) are staged as they are, [H, row_bytes] uint8: the image is `width` wide
-            W = packed_width(hip_opt(cfg, "raw_norm"), frames[0]) or W
+            W = RawLayout.from_raw_norm(hip_opt(cfg, "raw_norm"), frames[0]).width or W
             st.pin = None
             st.main, st.up = self.main, self.up
             for i, f in enumerate(frames):  # valid content for the capture-time launches' validation paths

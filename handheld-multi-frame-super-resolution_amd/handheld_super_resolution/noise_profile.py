@@ -15,9 +15,10 @@ import numpy as np
 import torch
 
 from . import _lib
+from .config import estimate_options
+from .raw_frames import FLOAT, check_device_frames, frame_list, summed_histogram
 
 HIST_SHAPE = (4, 64, 1024)
-SOURCES = ("given", "estimate")
 COLOURS = ("red", "green", "blue")
 MIN_TILES = 16
 
@@ -28,19 +29,11 @@ def noise_options(config):
     ValueError for anything else, and for "estimate" together with a config.noise_model.alpha that is not None: the
     caller gave a profile and asked for another."""
     nm = config.noise_model
-    source = str(nm.get("source", "given"))
-    if source not in SOURCES:
-        raise ValueError(f"config.noise_model.source {source!r}: given or estimate")
-    out = []
-    for key, default in (("frames", 1), ("min_tiles", MIN_TILES)):
-        v = nm.get(key, default)
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
-            raise ValueError(f"config.noise_model.{key} {v!r}: an integer >= 1")
-        out.append(int(v))
+    source, frames, min_tiles = estimate_options("noise_model", nm, MIN_TILES)
     if source == "estimate" and nm.get("alpha", None) is not None:
         raise ValueError("config.noise_model.source 'estimate' contradicts config.noise_model.alpha = "
                          f"{nm.get('alpha')!r}: leave alpha / beta None, or set source: given")
-    return source, out[0], out[1]
+    return source, frames, min_tiles
 
 
 def inv_gains(cfa_pattern, white_balance):
@@ -59,34 +52,14 @@ def inv_gains(cfa_pattern, white_balance):
 def noise_histogram(frames, cfa_pattern=None, white_balance=None):
     """Tile histogram of a list of device frames of one shape -> device int32 tensor [4, 64, 1024] holding the uint32
     counts (hhsr_noise_profile_hist).  float32 [H, W], normalised and white-balanced, H and W even; rows may be strided
-    (one row stride for all frames, elements of a row adjacent).  `cfa_pattern` None: a monochrome sensor.  The library is
-    called in chunks of MAX_BATCH frames and the chunks' counts are added."""
+    (raw_frames.check_device_frames).  `cfa_pattern` None: a monochrome sensor.  One call per chunk (summed_histogram)."""
     frames = list(frames)
-    if not frames:
-        raise ValueError("noise_histogram: no frame")
-    f0 = frames[0]
-    for t in frames:
-        if not (torch.is_tensor(t) and t.is_cuda):
-            raise RuntimeError("noise_histogram expects tensors on the GPU (the HIP path has no CPU fallback)")
-        if t.dim() != 2 or t.shape != f0.shape or t.dtype != f0.dtype or t.device != f0.device or t.stride() != f0.stride():
-            raise ValueError("noise_histogram: the frames need one 2-D shape, dtype, device and row stride")
-    if f0.dtype != torch.float32:
-        raise TypeError(f"noise_histogram: normalised float32 frames (got {f0.dtype})")
-    if f0.stride(1) != 1 and f0.shape[1] > 1:
-        raise ValueError("noise_histogram: the elements of a row must be adjacent in memory")
-    H, W = f0.shape
+    H, W, row_bytes, _ = check_device_frames("noise_histogram", frames, (FLOAT,))
     cfa = None if cfa_pattern is None else _lib.cfa_bytes(cfa_pattern)
     gains = _lib.floats(inv_gains(cfa_pattern, white_balance))
-    dev = f0.device
-    total = None
-    with torch.cuda.device(dev):
-        for i in range(0, len(frames), _lib.MAX_BATCH):
-            chunk = frames[i:i + _lib.MAX_BATCH]
-            hist = torch.empty(HIST_SHAPE, dtype=torch.int32, device=dev)
-            _lib.call("hhsr_noise_profile_hist", _lib.ptr_array(chunk), len(chunk), H, W, f0.stride(0) * 4, cfa, gains,
-                      _lib.ptr(hist), _lib.stream(dev))
-            total = hist if total is None else total.add_(hist)
-    return total
+    return summed_histogram(frames, HIST_SHAPE, lambda chunk, hist: _lib.call(
+        "hhsr_noise_profile_hist", _lib.ptr_array(chunk), len(chunk), H, W, row_bytes, cfa, gains, _lib.ptr(hist),
+        _lib.stream(hist.device)))
 
 
 def fit_profile(hist, cfa_pattern=None, min_tiles=MIN_TILES):
@@ -120,11 +93,6 @@ def estimate_noise_profile(frames, cfa_pattern=None, white_balance=None, min_til
     """(alpha, beta) of normalised, white-balanced float32 frames (one frame [H, W], a stack [n, H, W] or a list; host data
     is uploaded) -> the dict of fit_profile.  One pass over the frames on the GPU, 1 MiB back to the host, one host
     synchronisation."""
-    if torch.is_tensor(frames) or isinstance(frames, np.ndarray):
-        frames = [frames] if frames.ndim == 2 else [frames[i] for i in range(frames.shape[0])]
-    dev = None
-    for f in frames:
-        if torch.is_tensor(f) and f.is_cuda:
-            dev = f.device
+    frames, dev = frame_list(frames)
     dev_frames = [_lib.f32c(f, dev) for f in frames]
     return fit_profile(noise_histogram(dev_frames, cfa_pattern, white_balance), cfa_pattern, min_tiles)

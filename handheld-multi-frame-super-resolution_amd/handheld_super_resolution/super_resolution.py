@@ -18,13 +18,20 @@ import atexit
 import os
 import threading
 import time
+from collections import namedtuple
 
 import numpy as np
 import torch
 
-from . import _lib
-from .config import hip_opt
-from .utils_image import compute_grey_images, compute_grey_images_batch
+from . import _lib, raw2rgb
+from .config import hip_opt, positive_int
+from .noise_profile import estimate_noise_profile, noise_options
+from .raw_frames import FLOAT, RawLayout, host_counts
+from .utils_dng import load_dng_burst
+from .utils_image import (apply_orientation, compute_grey_images, compute_grey_images_batch, encode_image, encode_jpeg,
+                          encode_png, frame_count_denoising_gauss, frame_count_denoising_median, frame_sharpness,
+                          jpeg_option, png_option, robustness_mask)
+from .white_balance import estimate_white_balance, wb_options
 from .utils import divide, add, getTime, timer
 from .alignment import init_alignment, build_gaussian_pyramids, align_batch, can_align_batch
 from .params import sanitize_config, update_snr_config
@@ -138,6 +145,7 @@ class BurstPipeline:
         self._inject_flows = hip_opt(config, "inject_flows")
         # frames given as integer sensor counts: {"black_levels": [R, G, B], "white_level": w} (see _ingest)
         self._raw_norm = hip_opt(config, "raw_norm")
+        self._layouts = {}  # (dtype, shape) of an integer frame -> its RawLayout under raw_norm
         # (before, after): the flow fields handed to this pipeline are row slices (views) of larger fields with that many
         # tile rows around them — the sub-image pipelines of distributed.py; see robustness.compute_s
         self.flow_rows = (0, 0)
@@ -170,14 +178,11 @@ class BurstPipeline:
         if (t.is_cuda and not staged) or self._raw_norm is None:
             raise ValueError("integer frames are sensor counts: give config.hip.raw_norm = {black_levels, white_level} "
                              "(host arrays), or pass normalised float frames")
-        from .utils_dng import normalize_burst, normalize_packed, packed_width
-
-        width = packed_width(self._raw_norm, t)
-        if width is not None:  # raw_norm["packing"]: the 10/12/14-bit bytes as the sensor or the DNG holds them
-            return normalize_packed(t, width, self._raw_norm["packing"], self._raw_norm["black_levels"],
-                                    self._raw_norm["white_level"], self.wb, self.cfa, device=self.device)
-        return normalize_burst(t, self._raw_norm["black_levels"], self._raw_norm["white_level"], self.wb, self.cfa,
-                               device=self.device)
+        key = (t.dtype, t.shape)
+        layout = self._layouts.get(key)
+        if layout is None:  # (once per frame shape: the packed row length is a call into the library)
+            layout = self._layouts[key] = RawLayout.from_raw_norm(self._raw_norm, t)
+        return layout.normalize(t, self.wb, self.cfa, self.device)
 
     def prefetch(self, imgs):
         """Queue the uploads of all page-locked host frames of a list NOW, back to back on one upload stream, instead of
@@ -616,10 +621,7 @@ def reference_options(config):
     select = str(sec.get("select", "first"))
     if select not in REFERENCE_SELECT:
         raise ValueError(f"config.reference.select {select!r}: first or sharpest")
-    cand = sec.get("candidates", REFERENCE_CANDIDATES)
-    if isinstance(cand, bool) or not isinstance(cand, (int, np.integer)) or cand < 1:
-        raise ValueError(f"config.reference.candidates {cand!r}: an integer >= 1")
-    return select, int(cand)
+    return select, positive_int("reference", "candidates", sec.get("candidates", REFERENCE_CANDIDATES))
 
 
 def candidate_count(config, n_burst):
@@ -636,40 +638,18 @@ def pick_reference(scores):
     return arg
 
 
-def select_reference(ref, comp, config, cfa_pattern=None, packing=None, width=None):
+def select_reference(ref, comp, config, cfa_pattern=None, layout=RawLayout(FLOAT)):
     """(index, scores): the sharpest of the burst's first config.reference.candidates frames (clamped to the burst's
     length), [ref, comp[0], ..., comp[K - 2]] in burst order, scored on the GPU by utils_image.frame_sharpness; `index` by
     pick_reference, `scores` a float64 ndarray [K].  Host frames are uploaded in their own form — float32, uint16 counts
-    or, with `packing`, the packed uint8 rows — and scored as they are: integer counts are not normalised first.
-    `cfa_pattern`: the burst's (default: config.exif's); ignored with `mode: grey`, whose score has no CFA.  One host
-    synchronisation (the scores decide what is uploaded and merged next)."""
-    from .utils_image import frame_sharpness
-
+    or, with the RawLayout of a packed burst, the packed uint8 rows — and scored as they are: integer counts are not
+    normalised first.  `cfa_pattern`: the burst's (default: config.exif's); ignored with `mode: grey`, whose score has no
+    CFA.  One host synchronisation (the scores decide what is uploaded and merged next)."""
     k = candidate_count(config, 1 + len(comp))
     dev = _device()
-    frames = []
-    for f in [ref] + [comp[i] for i in range(k - 1)]:
-        if not torch.is_tensor(f):
-            a = np.asarray(f)
-            if np.issubdtype(a.dtype, np.integer) and packing is None and a.dtype != np.uint16:
-                if a.size and (int(a.min()) < 0 or int(a.max()) > 65535):
-                    raise ValueError("sensor counts outside the uint16 range")
-                a = a.astype(np.uint16)
-            elif not np.issubdtype(a.dtype, np.integer):
-                a = a.astype(np.float32, copy=False)
-            f = torch.as_tensor(np.ascontiguousarray(a))
-        if f.dtype.is_floating_point and f.dtype != torch.float32:
-            f = f.to(torch.float32)
-        frames.append(f.to(dev, non_blocking=True))
-    if config.mode == "grey":
-        cfa = None
-    else:
-        cfa = cfa_pattern if cfa_pattern is not None else config.exif.cfa_pattern
-        cfa = np.asarray(cfa).tolist()
-    if packing is not None:
-        packing = np.asarray(packing).item()
-        width = None if width is None else int(np.asarray(width))
-    scores = frame_sharpness(frames, cfa, packing=packing, width=width).cpu().numpy()
+    frames = [layout.upload(f, dev) for f in [ref] + [comp[i] for i in range(k - 1)]]
+    cfa = None if config.mode == "grey" else np.asarray(config.exif.cfa_pattern if cfa_pattern is None else cfa_pattern).tolist()
+    scores = frame_sharpness(frames, cfa, packing=layout.packing, width=layout.width).cpu().numpy()
     return pick_reference(scores), scores
 
 
@@ -686,47 +666,28 @@ def reorder_burst(ref, comp, index):
     return comp[j], [ref] + comp[:j] + comp[j + 1:]
 
 
-def estimate_burst_profile(ref_raw, raw_comp, burst, config, n_frames=1, min_tiles=16):
+def _first_frames(ref_raw, raw_comp, n_frames):
+    """The reference frame and the next n_frames - 1 frames of the burst (clamped to its length)."""
+    return [ref_raw] + [raw_comp[i] for i in range(max(1, min(int(n_frames), 1 + len(raw_comp))) - 1)]
+
+
+def estimate_burst_profile(ref_raw, raw_comp, burst, layout, config, n_frames=1, min_tiles=16):
     """The noise profile of a burst (noise_profile.estimate_noise_profile) from its reference frame `ref_raw`, already
-    normalised, and with n_frames > 1 from the next n_frames - 1 frames of `raw_comp` as well (clamped to the burst's
-    length); integer frames are normalised as process() normalises the reference frame.  `mode: grey`: no CFA, unit gains."""
-    from .noise_profile import estimate_noise_profile
-    from .utils_dng import infer_width, normalize_burst, normalize_packed
-
-    frames = [ref_raw]
-    for i in range(max(1, min(int(n_frames), 1 + len(raw_comp))) - 1):
-        f = raw_comp[i]
-        if not torch.is_tensor(f) and np.issubdtype(np.asarray(f).dtype, np.integer):
-            norm = (burst["black_levels"], burst["white_level"], burst["white_balance"], burst["cfa_pattern"])
-            if burst.get("packing", None) is not None:
-                packing = np.asarray(burst["packing"]).item()
-                width = burst.get("width", None)
-                width = infer_width(np.asarray(f).shape[-1], packing) if width is None else int(np.asarray(width))
-                f = normalize_packed(np.asarray(f), width, packing, *norm)
-            else:
-                f = normalize_burst(np.asarray(f), *norm)
-        frames.append(f)
-    if config.mode == "grey":
-        return estimate_noise_profile(frames, None, None, min_tiles)
-    return estimate_noise_profile(frames, np.asarray(burst["cfa_pattern"]).tolist(),
-                                  [float(v) for v in list(burst["white_balance"])[:3]], min_tiles)
+    normalised, and with n_frames > 1 from the next n_frames - 1 frames of `raw_comp` as well (clamped to the burst's length);
+    integer frames are normalised like the reference frame, by the burst's RawLayout.  `mode: grey`: no CFA, unit gains."""
+    frames = [layout.normalize(np.asarray(f), burst["white_balance"], burst["cfa_pattern"]) if i and host_counts(f) else f
+              for i, f in enumerate(_first_frames(ref_raw, raw_comp, n_frames))]
+    cfa_wb = (None, None) if config.mode == "grey" else (np.asarray(burst["cfa_pattern"]).tolist(),
+                                                         [float(v) for v in list(burst["white_balance"])[:3]])
+    return estimate_noise_profile(frames, *cfa_wb, min_tiles)
 
 
-def estimate_burst_white_balance(ref_raw, raw_comp, burst, n_frames=1, min_tiles=16):
+def estimate_burst_white_balance(ref_raw, raw_comp, burst, layout, n_frames=1, min_tiles=16):
     """The white balance of a burst of integer counts (white_balance.estimate_white_balance) from its reference frame
     `ref_raw` and, with n_frames > 1, from the next n_frames - 1 frames of `raw_comp` as well (clamped to the burst's
-    length): uint16 counts or, with burst["packing"], packed rows, uploaded and measured as they are."""
-    from .utils_dng import infer_width
-    from .white_balance import estimate_white_balance
-
-    frames = [ref_raw] + [raw_comp[i] for i in range(max(1, min(int(n_frames), 1 + len(raw_comp))) - 1)]
-    packing = width = None
-    if burst.get("packing", None) is not None:
-        packing = np.asarray(burst["packing"]).item()
-        width = burst.get("width", None)
-        width = infer_width(np.asarray(ref_raw).shape[-1], packing) if width is None else int(np.asarray(width))
-    return estimate_white_balance(frames, np.asarray(burst["cfa_pattern"]).tolist(), burst["black_levels"],
-                                  float(burst["white_level"]), packing, width, min_tiles)
+    length): uint16 counts or, by the burst's RawLayout, packed rows, uploaded and measured as they are."""
+    return estimate_white_balance(_first_frames(ref_raw, raw_comp, n_frames), np.asarray(burst["cfa_pattern"]).tolist(),
+                                  layout.black_levels, layout.white_level, layout.packing, layout.width, min_tiles)
 
 
 def prepare_config(config, ref_raw, alpha=None, beta=None, cfa_pattern=None, white_balance=None, iso=100,
@@ -764,124 +725,76 @@ def prepare_config(config, ref_raw, alpha=None, beta=None, cfa_pattern=None, whi
     return config
 
 
-def process(burst_path, config):
-    """process(burst_path, config) -> (float32 ndarray [sH, sW, 3], debug_dict)   (reference :203-360).
+OutputOptions = namedtuple("OutputOptions", "format dtype quality restart_mcus subsampling huffman filter interval_bytes",
+                           defaults=(None,) * 6)
+IntakeOptions = namedtuple("IntakeOptions", "ref_select noise_source noise_frames noise_min_tiles wb_source wb_frames wb_min_tiles")
 
-    `burst_path` is either a burst held in memory / in an .npz file — a mapping with keys ``ref`` [H,W],
-    ``comp`` [N-1,H,W], ``cfa_pattern`` [2,2], ``white_balance`` [>=3], ``alpha``, ``beta`` and optionally
-    ``iso``, ``std_curve``, ``diff_curve``, ``orientation`` (EXIF 1..8), ``xyz2cam`` (3x3, DNG ColorMatrix1, for
-    ``postprocessing.do_color_correction``) — ``cfa_pattern`` / ``white_balance`` may be left out with ``mode: grey``
-    (monochrome sensors: channel 0 of the result is the image, channels 1 and 2 are NaN like the reference's); ref / comp are either normalised white-balanced float RAW or integer
-    sensor counts with ``black_levels`` and ``white_level`` (normalised on the GPU like utils_dng.py:149-160), either
-    uint16 or, with ``packing`` (a name of utils_dng.PACKINGS) and ``width`` (may be left out when the rows hold no
-    padding), the packed 10/12/14-bit rows as uint8 [H, row_bytes] —
-    or a folder of .dng files, which needs rawpy + exifread like the reference (absent from this image:
-    ImportError).  Noise curves: given in the burst, or ``config.noise_model.estimator``: "monte_carlo" (default — the
-    reference's estimator run_fast_MC, super_resolution.py:252, whose curves include the clipping of the noisy samples
-    to [0, 1]: near black and near saturation sigma_t and d_t are up to ~1.6x smaller than the un-clipped law; seeded by
-    ``config.noise_model.seed``, default 0, so process() is reproducible where the reference is not, D18),
-    "monte_carlo_hip" (the same estimator as one fused kernel of the C library, hhsr_noise_mc: its own seeded stream,
-    stated in include/hhsr.h, so its curves differ from "monte_carlo" by Monte-Carlo noise) or
-    "analytic" (the un-clipped limit, synthetic.noise_curves — what prepare_config() uses when called directly).
-    After main(): the frame-count denoisers (``accumulated_robustness_denoiser.median / .gauss``), then
-    ``postprocessing`` (colour matrix, unsharp mask, devignetting, gamma — ON by default like the reference's YAML; tone
-    mapping raises NotImplementedError) and the EXIF orientation, all on the GPU (utils_image.py, raw2rgb.py); only the
-    finished image is copied to the host.  ``config.output = {"dtype": "uint8" | "uint16"}`` (optional; absent or "float32":
-    the float32 image as above): the finished, oriented image is quantised on the GPU — rint(clip(nan_to_num(x), 0, 1) * M),
-    half to even, M = 255 / 65535: skimage's img_as_ubyte and the reference's 16-bit TIFF rule (hhsr_encode_image) — and only
-    the integer image is copied; the result is an ndarray of that dtype, [sH, sW, 3] or, with ``mode: grey``, [sH, sW]
-    (channel 0).  With ``robustness.save_mask`` as well, ``debug_dict["robustness mask"]`` is the reference's mask image:
-    uint8 [sH, sW], accumulated robustness / number of comparison frames, nearest neighbour (hhsr_encode_mask).
+
+def output_options(config):
+    """The optional section ``config.output`` (not in the reference schema) as an OutputOptions (None: a key the format does
+    not read); anything it cannot hold is a ValueError here, before the burst is touched, not after it has been merged.
+    ``config.output = {"dtype": "uint8" | "uint16"}`` (absent or "float32": the float32 image): the finished, oriented image
+    is quantised on the GPU — rint(clip(nan_to_num(x), 0, 1) * M), half to even, M = 255 / 65535: skimage's img_as_ubyte and
+    the reference's 16-bit TIFF rule (hhsr_encode_image) — and only the integer image is copied; the result is an ndarray of
+    that dtype, [sH, sW, 3] or, with ``mode: grey``, [sH, sW] (channel 0).
     ``config.output = {"format": "jpeg", "quality": 90, "restart_mcus": ...}`` (``format`` absent or "raw": everything above,
-    unchanged): the result is instead the complete baseline JPEG file of the uint8 image as a 1-D uint8 ndarray, coded on
-    the GPU (utils_image.encode_jpeg; one component with ``mode: grey``; write it with utils_image.save_jpeg).  ``dtype``
-    may be absent or "uint8" then, anything else is a ValueError; the robustness mask stays the uint8 array it is.
-    With ``format: jpeg``, ``subsampling: 444 | 420`` (string or integer; 420 halves the chroma planes and is refused with
-    ``mode: grey``) and ``huffman: standard | optimized`` (tables made for the image: a smaller file for one more
-    synchronisation) choose the encoder's options; both keys are read only then, anything else is a ValueError before the
-    burst is merged.
+    unchanged): the result is instead the complete baseline JPEG file of the uint8 image as a 1-D uint8 ndarray, coded on the
+    GPU (utils_image.encode_jpeg; one component with ``mode: grey``; write it with utils_image.save_jpeg).  ``dtype`` may be
+    absent or "uint8" then, anything else is a ValueError.  ``subsampling: 444 | 420`` (string or integer; 420 halves the
+    chroma planes and is refused with ``mode: grey``) and ``huffman: standard | optimized`` (tables made for the image: a
+    smaller file for one more synchronisation) choose the encoder's options; both keys are read only with ``format: jpeg``,
+    anything else is a ValueError.
     ``config.output = {"format": "png", "dtype": "uint8" | "uint16", "filter": ..., "interval_bytes": ...}``: the result is
     the complete PNG file of the uint8 (default) or uint16 image as a 1-D uint8 ndarray, filtered and deflate-coded on the
     GPU (utils_image.encode_png; colour type 0 with ``mode: grey``; write it with utils_image.save_png_bytes).  ``filter``:
     none | sub | up | average | paeth | adaptive (default); ``interval_bytes``: 1 .. 2^20 (default
-    utils_image.PNG_INTERVAL_BYTES).  ``dtype: float32``, another filter name or interval is a ValueError before the burst
-    is merged; the robustness mask stays the uint8 array it is.
-    ``config.reference = {"select": "first" | "sharpest", "candidates": 3}`` (optional; absent or "first": ``ref`` is the
-    base frame, as in the reference, which takes file 0 — nothing below runs then): with "sharpest" the first ``candidates``
-    frames of the burst (clamped to its length) are scored on the GPU in the form they come in (select_reference,
-    hhsr_frame_sharpness), the sharpest becomes ``ref`` and the others keep their order as ``comp``; everything derived from
-    the reference frame — its brightness and the SNR-based parameters, the early normalisation of an integer burst —
-    follows the chosen frame.  ``debug_dict["reference index"]`` is its position in the original burst,
-    ``debug_dict["sharpness"]`` the candidates' scores (float64 ndarray).  The candidates are uploaded once for the score
-    and again by main().  For a folder of .dng files the frame arrays are reordered; the tags (noise profile, ISO,
-    orientation, colour matrix) stay those of file 0.  Another ``select`` or ``candidates`` < 1 is a ValueError before
-    anything is uploaded.
-    ``config.noise_model.source = "given" | "estimate"`` (optional; absent or "given": everything above, unchanged), with
-    ``noise_model.frames`` (default 1) and ``noise_model.min_tiles`` (default 16): with "estimate" the noise profile is
-    measured on the GPU (noise_profile.estimate_noise_profile: hhsr_noise_profile_hist, hhsr_noise_profile_fit) from the
-    normalised reference frame — after the reference selection — and with ``frames`` > 1 from the next frames as well
-    (clamped to the burst's length); the burst's own ``alpha`` / ``beta`` are ignored, the estimate feeds the curve
-    estimators and prepare_config() like a given pair (``config.noise_model.alpha`` / ``.beta`` hold it afterwards) and
-    ``debug_dict["noise profile"]`` is the estimator's dict (alpha, beta, per_colour, bins_used).  On a textured scene
-    the estimate is an upper bound (noise_profile.py).  A ``config.noise_model.alpha`` that is not None together with
-    "estimate", another ``source``, ``frames`` or ``min_tiles`` < 1 is a ValueError before anything is uploaded — so a
-    configuration object that went through an estimating call is reset (alpha: None) before the next.
-    ``config.white_balance = {"source": "given" | "estimate", "frames": 1, "min_tiles": 16}`` (optional; absent or "given":
-    the burst's ``white_balance``, and nothing below runs): with "estimate" a Bayer burst of integer counts needs no
-    ``white_balance`` key — the gains are measured on the GPU (white_balance.estimate_white_balance:
-    hhsr_white_balance_hist, hhsr_white_balance_fit) from the reference frame's counts, after the reference selection and
-    before anything is normalised, with ``frames`` > 1 from the next frames' counts as well (clamped to the burst's length).
-    The burst's own ``white_balance`` is ignored; the estimate is what the normalisation of every frame, the noise
-    estimate and prepare_config() / ``config.exif`` see, and ``debug_dict["white balance"]`` is the estimator's dict
-    (white_balance, tiles, tiles_gated).  It is a grey-world estimate: a scene whose balanced channel means differ is
-    estimated wrong by that difference.  ``mode: grey``, frames that are not integer counts (float frames are already
-    balanced; a folder of .dng files comes back normalised), another ``source``, ``frames`` or ``min_tiles`` < 1 is a
-    ValueError before anything is uploaded; fewer than ``min_tiles`` usable tiles is the ValueError of
-    fit_white_balance."""
-    import os
-
-    from .utils_dng import infer_width, load_dng_burst, normalize_burst, normalize_packed
-
-    out_cfg = config.get("output", None) or {}  # optional section, not in the reference schema
-    out_format = str(out_cfg.get("format", "raw"))
-    if out_format not in ("raw", "jpeg", "png"):
-        raise ValueError(f"config.output.format {out_format!r}: raw, jpeg or png")
-    out_dtype = str(out_cfg.get("dtype", "uint8" if out_format in ("jpeg", "png") else "float32"))
-    if out_dtype not in ("float32", "uint8", "uint16"):
-        raise ValueError(f"config.output.dtype {out_dtype!r}: float32, uint8 or uint16")
-    if out_format == "jpeg" and out_dtype != "uint8":
-        raise ValueError(f"config.output.format jpeg holds 8-bit samples: output.dtype {out_dtype!r} contradicts it")
-    if out_format == "jpeg":  # (refused now, not after the burst has been merged)
-        if not 1 <= int(out_cfg.get("quality", 90)) <= 100:
-            raise ValueError(f"config.output.quality {out_cfg.get('quality')!r}: 1 .. 100")
-        if out_cfg.get("restart_mcus", None) is not None and not 1 <= int(out_cfg.get("restart_mcus")) <= 65535:
-            raise ValueError(f"config.output.restart_mcus {out_cfg.get('restart_mcus')!r}: 1 .. 65535")
-        from .utils_image import jpeg_option
-
-        out_sub = jpeg_option("subsampling", out_cfg.get("subsampling", "444"))
-        out_huffman = jpeg_option("huffman", out_cfg.get("huffman", "standard"))
-        if out_sub == "420" and config.mode == "grey":
+    utils_image.PNG_INTERVAL_BYTES).  ``dtype: float32``, another filter name or interval is a ValueError."""
+    sec = config.get("output", None) or {}
+    fmt = str(sec.get("format", "raw"))
+    if fmt not in ("raw", "jpeg", "png"):
+        raise ValueError(f"config.output.format {fmt!r}: raw, jpeg or png")
+    dtype = str(sec.get("dtype", "uint8" if fmt in ("jpeg", "png") else "float32"))
+    if dtype not in ("float32", "uint8", "uint16"):
+        raise ValueError(f"config.output.dtype {dtype!r}: float32, uint8 or uint16")
+    if fmt == "jpeg":
+        if dtype != "uint8":
+            raise ValueError(f"config.output.format jpeg holds 8-bit samples: output.dtype {dtype!r} contradicts it")
+        if not 1 <= int(sec.get("quality", 90)) <= 100:
+            raise ValueError(f"config.output.quality {sec.get('quality')!r}: 1 .. 100")
+        if sec.get("restart_mcus", None) is not None and not 1 <= int(sec.get("restart_mcus")) <= 65535:
+            raise ValueError(f"config.output.restart_mcus {sec.get('restart_mcus')!r}: 1 .. 65535")
+        subsampling = jpeg_option("subsampling", sec.get("subsampling", "444"))
+        huffman = jpeg_option("huffman", sec.get("huffman", "standard"))
+        if subsampling == "420" and config.mode == "grey":
             raise ValueError("config.output.subsampling 420 needs three components: mode grey writes one")
-    if out_format == "png":  # (refused now as well)
-        if out_dtype == "float32":
+        return OutputOptions(fmt, dtype, sec.get("quality", 90), sec.get("restart_mcus", None), subsampling, huffman)
+    if fmt == "png":
+        if dtype == "float32":
             raise ValueError("config.output.format png holds 8- or 16-bit samples: output.dtype 'float32' contradicts it")
-        from .utils_image import png_option
+        return OutputOptions(fmt, dtype, filter=png_option("filter", sec.get("filter", "adaptive")),
+                             interval_bytes=png_option("interval_bytes", sec.get("interval_bytes", None)))
+    return OutputOptions(fmt, dtype)
 
-        out_filter = png_option("filter", out_cfg.get("filter", "adaptive"))
-        out_interval = png_option("interval_bytes", out_cfg.get("interval_bytes", None))
-    ref_select, _ = reference_options(config)  # (refused now as well)
-    from .noise_profile import noise_options
 
-    noise_source, noise_frames, noise_min_tiles = noise_options(config)  # (and this)
-    from .white_balance import wb_options
-
-    wb_source, wb_frames, wb_min_tiles = wb_options(config)  # (and this)
-    if wb_source == "estimate":
+def intake_options(burst_path, config):
+    """reference_options, noise_profile.noise_options and white_balance.wb_options as an IntakeOptions, checked in that
+    order, plus the refusals of ``white_balance.source: estimate`` that need no burst — ``mode: grey`` and a folder of .dng
+    files, which comes back normalised: each a ValueError before the burst is touched or anything is uploaded."""
+    intake = IntakeOptions(reference_options(config)[0], *noise_options(config), *wb_options(config))
+    if intake.wb_source == "estimate":
         if config.mode == "grey":
             raise ValueError("config.white_balance.source 'estimate' with mode grey: a monochrome sensor has no white balance")
         if isinstance(burst_path, (str, os.PathLike)) and not str(burst_path).endswith(".npz"):
             raise ValueError("config.white_balance.source 'estimate' needs integer sensor counts: a folder of .dng files "
                              "comes back normalised and balanced by its own AsShotNeutral")
+    return intake
+
+
+def load_burst(burst_path, config):
+    """The burst mapping of process(): `burst_path` itself, the arrays of an .npz file, or a folder of .dng files, which
+    needs rawpy + exifread like the reference (absent from this image: ImportError) and takes the noise profile, ISO,
+    orientation and colour matrix from the tags of file 0.  ``mode: grey``: ``cfa_pattern`` / ``white_balance`` are filled in."""
+    burst = burst_path
     if isinstance(burst_path, (str, os.PathLike)) and str(burst_path).endswith(".npz"):
         burst = dict(np.load(burst_path))
     elif isinstance(burst_path, (str, os.PathLike)):
@@ -897,56 +810,84 @@ def process(burst_path, config):
             burst["orientation"] = tags["Image Orientation"].values[0]
         if "Image Tag 0xC621" in tags:  # DNG ColorMatrix1 (raw2rgb.py:12-27)
             burst["xyz2cam"] = np.array([x.decimal() for x in tags["Image Tag 0xC621"].values], np.float32).reshape(3, 3)
-    else:
-        burst = burst_path
     if config.mode == "grey":  # monochrome sensor: no colour filter array, no white balance (both unused by main())
         burst = dict(burst)
         burst.setdefault("cfa_pattern", [[0, 1], [1, 2]])
         burst.setdefault("white_balance", [1.0, 1.0, 1.0])
+    return burst
+
+
+def merge_stage(burst, intake, config):
+    """From the burst mapping to main(): (merged image, debug_dict, number of comparison frames), in this order.
+    ``reference.select: sharpest`` (absent or "first": ``ref`` is the base frame, as in the reference, which takes file 0 —
+    nothing of this step runs then): the first ``candidates`` frames of the burst (clamped to its length) are scored on the
+    GPU in the form they come in (select_reference, hhsr_frame_sharpness), the sharpest becomes ``ref`` and the others keep
+    their order as ``comp``; everything derived from the reference frame — its brightness and the SNR-based parameters, the
+    early normalisation of an integer burst — follows the chosen frame.  ``debug_dict["reference index"]`` is its position in
+    the original burst, ``debug_dict["sharpness"]`` the candidates' scores (float64 ndarray).  The candidates are uploaded
+    once for the score and again by main().  For a folder of .dng files the frame arrays are reordered; the tags (noise
+    profile, ISO, orientation, colour matrix) stay those of file 0.
+    ``white_balance.source: estimate`` (absent or "given": the burst's ``white_balance``, and nothing of this step runs): a
+    Bayer burst of integer counts needs no ``white_balance`` key — the gains are measured on the GPU
+    (white_balance.estimate_white_balance: hhsr_white_balance_hist, hhsr_white_balance_fit) from the reference frame's
+    counts, after the reference selection and before anything is normalised, with ``frames`` > 1 from the next frames' counts
+    as well (clamped to the burst's length).  The burst's own ``white_balance`` is ignored; the estimate is what the
+    normalisation of every frame, the noise estimate and prepare_config() / ``config.exif`` see, and ``debug_dict["white
+    balance"]`` is the estimator's dict (white_balance, tiles, tiles_gated).  It is a grey-world estimate: a scene whose
+    balanced channel means differ is estimated wrong by that difference.  Frames that are not integer counts (float frames
+    are already balanced) are a ValueError before anything is uploaded; fewer than ``min_tiles`` usable tiles is the
+    ValueError of fit_white_balance.
+    Integer frames (raw_frames.RawLayout.from_burst) are sensor counts + metadata: the normalisation / white balance of
+    utils_dng.py:149-160, on the GPU.  The reference frame now (its brightness picks the SNR-based parameters); the other
+    frames stay integer host arrays and are uploaded as counts or packed rows — half the bytes of float32 frames or less —
+    and normalised frame by frame on the pipeline streams (BurstPipeline._ingest, told by ``config.hip.raw_norm``),
+    overlapping the other frames' kernels.
+    ``noise_model.source: estimate`` (absent or "given": the burst's ``alpha`` / ``beta``), with ``noise_model.frames``
+    (default 1) and ``noise_model.min_tiles`` (default 16): the noise profile is measured on the GPU
+    (noise_profile.estimate_noise_profile: hhsr_noise_profile_hist, hhsr_noise_profile_fit) from the normalised reference
+    frame — after the reference selection — and with ``frames`` > 1 from the next frames as well (clamped to the burst's
+    length); the burst's own ``alpha`` / ``beta`` are ignored, the estimate feeds the curve estimators and prepare_config()
+    like a given pair (``config.noise_model.alpha`` / ``.beta`` hold it afterwards — so a configuration object that went
+    through an estimating call is reset (alpha: None) before the next, or noise_options refuses it) and ``debug_dict["noise
+    profile"]`` is the estimator's dict (alpha, beta, per_colour, bins_used).  On a textured scene the estimate is an upper
+    bound (noise_profile.py).
+    Noise curves: given in the burst, or ``config.noise_model.estimator``: "monte_carlo" (default — the reference's estimator
+    run_fast_MC, super_resolution.py:252, whose curves include the clipping of the noisy samples to [0, 1]: near black and
+    near saturation sigma_t and d_t are up to ~1.6x smaller than the un-clipped law; seeded by
+    ``config.noise_model.seed``, default 0, so process() is reproducible where the reference is not, D18), "monte_carlo_hip"
+    (the same estimator as one fused kernel of the C library, hhsr_noise_mc: its own seeded stream, stated in include/hhsr.h,
+    so its curves differ from "monte_carlo" by Monte-Carlo noise) or "analytic" (the un-clipped limit, synthetic.noise_curves
+    — what prepare_config() uses when called directly)."""
     ref_raw, raw_comp = burst["ref"], burst["comp"]
-    if wb_source == "estimate" and (torch.is_tensor(ref_raw) or not np.issubdtype(np.asarray(ref_raw).dtype, np.integer)):
+    layout = RawLayout.from_burst(burst, ref_raw)
+    if intake.wb_source == "estimate" and not layout.is_counts:
         raise ValueError("config.white_balance.source 'estimate' needs integer sensor counts (with black_levels and "
                          "white_level): float frames are taken as normalised and already white-balanced")
-    ref_index = ref_scores = None
-    if ref_select == "sharpest":  # the chosen frame is `ref` from here on
-        ref_index, ref_scores = select_reference(ref_raw, raw_comp, config, burst["cfa_pattern"], burst.get("packing", None),
-                                                 burst.get("width", None))
-        ref_raw, raw_comp = reorder_burst(ref_raw, raw_comp, ref_index)
-    wb_estimate = None
-    if wb_source == "estimate":  # the burst's own white_balance is ignored
-        wb_estimate = estimate_burst_white_balance(ref_raw, raw_comp, burst, wb_frames, wb_min_tiles)
+    debug = {}
+    if intake.ref_select == "sharpest":  # the chosen frame is `ref` from here on
+        index, scores = select_reference(ref_raw, raw_comp, config, burst["cfa_pattern"], layout)
+        ref_raw, raw_comp = reorder_burst(ref_raw, raw_comp, index)
+        debug.update({"reference index": int(index), "sharpness": np.asarray(scores, np.float64)})
+    if intake.wb_source == "estimate":  # the burst's own white_balance is ignored
+        wb_estimate = estimate_burst_white_balance(ref_raw, raw_comp, burst, layout, intake.wb_frames, intake.wb_min_tiles)
         burst = dict(burst, white_balance=wb_estimate["white_balance"])
-    if not torch.is_tensor(ref_raw) and np.issubdtype(np.asarray(ref_raw).dtype, np.integer):
-        # sensor counts + metadata: the normalisation / white balance of utils_dng.py:149-160, on the GPU.  The
-        # reference frame now (its brightness picks the SNR-based parameters); the other frames stay integer host arrays
-        # and are uploaded as counts — half the bytes of float32 frames — and normalised frame by frame on the pipeline
-        # streams (BurstPipeline._ingest), overlapping the other frames' kernels
-        raw_norm = {"black_levels": [float(v) for v in list(burst["black_levels"])[:3]], "white_level": float(burst["white_level"])}
-        if burst.get("packing", None) is not None:  # ref / comp are uint8 packed rows (utils_dng.PACKINGS) and stay so
-            packing = np.asarray(burst["packing"]).item()
-            width = burst.get("width", None)
-            width = infer_width(np.asarray(ref_raw).shape[-1], packing) if width is None else int(np.asarray(width))
-            if width is None:
-                raise ValueError("packed burst: give 'width' (the rows are longer than their pixels' bytes)")
-            ref_raw = normalize_packed(np.asarray(ref_raw), width, packing, burst["black_levels"], burst["white_level"],
-                                       burst["white_balance"], burst["cfa_pattern"])
-            raw_norm.update(packing=packing, width=width)
-        else:
-            ref_raw = normalize_burst(np.asarray(ref_raw), burst["black_levels"], burst["white_level"],
-                                      burst["white_balance"], burst["cfa_pattern"])
+    if layout.is_counts:
+        ref_raw = layout.normalize(np.asarray(ref_raw), burst["white_balance"], burst["cfa_pattern"])
         raw_comp = [np.asarray(f) for f in raw_comp]
-        config.hip = dict(getattr(config, "hip", None) or {}, raw_norm=raw_norm)  # (a fresh mapping: the caller's is not edited)
-        brightness_src = ref_raw.mean().item()
+        config.hip = dict(getattr(config, "hip", None) or {}, raw_norm=layout.raw_norm())  # (a fresh mapping: the caller's is not edited)
+        ref_for_stats = np.full((1, 1), ref_raw.mean().item(), np.float32)
     else:
         ref_raw = np.asarray(ref_raw, dtype=np.float32) if not torch.is_tensor(ref_raw) else ref_raw
         raw_comp = np.asarray(raw_comp, dtype=np.float32) if not torch.is_tensor(raw_comp) else raw_comp
-        brightness_src = None
+        ref_for_stats = ref_raw
     std_curve, diff_curve = burst.get("std_curve"), burst.get("diff_curve")
     alpha, beta = burst.get("alpha"), burst.get("beta")
-    noise_profile = None
-    if noise_source == "estimate":  # the burst's own alpha / beta are ignored
-        noise_profile = estimate_burst_profile(ref_raw, raw_comp, burst, config, noise_frames, noise_min_tiles)
-        alpha, beta = noise_profile["alpha"], noise_profile["beta"]
+    if intake.noise_source == "estimate":  # the burst's own alpha / beta are ignored
+        debug["noise profile"] = estimate_burst_profile(ref_raw, raw_comp, burst, layout, config, intake.noise_frames,
+                                                        intake.noise_min_tiles)
+        alpha, beta = debug["noise profile"]["alpha"], debug["noise profile"]["beta"]
+    if intake.wb_source == "estimate":
+        debug["white balance"] = wb_estimate
     estimator = config.noise_model.get("estimator", "monte_carlo")
     if (std_curve is None or diff_curve is None) and estimator in ("monte_carlo", "monte_carlo_hip"):
         from .fast_monte_carlo import run_fast_MC  # the reference's estimator (super_resolution.py:252), seeded
@@ -955,33 +896,29 @@ def process(burst_path, config):
             alpha, beta = config.noise_model.alpha, config.noise_model.beta
         std_curve, diff_curve = run_fast_MC(float(alpha), float(beta), seed=int(config.noise_model.get("seed", 0)),
                                             engine="hip" if estimator == "monte_carlo_hip" else "torch")
-    ref_for_stats = ref_raw if brightness_src is None else np.full((1, 1), brightness_src, np.float32)
     prepare_config(config, ref_for_stats, alpha, beta, burst["cfa_pattern"], burst["white_balance"],
-                   int(burst.get("iso", 100)), std_curve, diff_curve,
-                   shape=tuple(ref_raw.shape))
+                   int(burst.get("iso", 100)), std_curve, diff_curve, shape=tuple(ref_raw.shape))
     out, debug_dict = main(ref_raw, raw_comp, config)
-    if ref_index is not None:
-        debug_dict["reference index"] = int(ref_index)
-        debug_dict["sharpness"] = np.asarray(ref_scores, np.float64)
-    if noise_profile is not None:
-        debug_dict["noise profile"] = noise_profile
-    if wb_estimate is not None:
-        debug_dict["white balance"] = wb_estimate
+    debug_dict.update(debug)
+    return out, debug_dict, len(raw_comp)
 
-    # ---- after the path (reference super_resolution.py:303-356), on the device --------------------------------------
-    from . import raw2rgb
-    from .utils_image import apply_orientation, frame_count_denoising_gauss, frame_count_denoising_median
 
+def finish(out, debug_dict, burst, n_comp, output, config):
+    """After main() (reference super_resolution.py:303-356), all on the GPU (utils_image.py, raw2rgb.py; only the finished
+    image is copied to the host): the frame-count denoisers (``accumulated_robustness_denoiser.median / .gauss``), then
+    ``postprocessing`` (colour matrix, unsharp mask, devignetting, gamma — ON by default like the reference's YAML; tone
+    mapping is the device implementation of the algorithm include/hhsr.h restates, never compared with an OpenCV run:
+    raw2rgb.postprocess with restated_tonemapping=True) and the EXIF orientation, then what `output` (output_options) asks
+    for.  With an integer dtype and ``robustness.save_mask``, ``debug_dict["robustness mask"]`` is the reference's mask
+    image: uint8 [sH, sW], accumulated robustness / number of comparison frames, nearest neighbour (hhsr_encode_mask); it
+    stays that uint8 array with ``format: jpeg`` and ``png``."""
     den = config.accumulated_robustness_denoiser
-    compat = config.get("compat", None) or {}
-    half_index = bool(compat.get("post_denoiser_half_index", True))
-    if den.median.enabled:
-        out = frame_count_denoising_median(out, debug_dict["accumulated robustness"], den.median, scale=config.scale,
-                                           half_index=half_index, mode=config.mode)
-    if den.gauss.enabled:
-        out = frame_count_denoising_gauss(out, debug_dict["accumulated robustness"], den.gauss, scale=config.scale,
-                                          half_index=half_index, mode=config.mode)
-    ori = int(burst.get("orientation", 1))  # EXIF 'Image Orientation' (reference :346-352); 1 when the burst has none
+    half_index = bool((config.get("compat", None) or {}).get("post_denoiser_half_index", True))
+    for stage, denoise in ((den.median, frame_count_denoising_median), (den.gauss, frame_count_denoising_gauss)):
+        if stage.enabled:
+            out = denoise(out, debug_dict["accumulated robustness"], stage, scale=config.scale, half_index=half_index,
+                          mode=config.mode)
+    ori = int(burst.get("orientation", 1))  # EXIF 'Image Orientation' (reference :346-352)
     pp = config.postprocessing
     if pp.enabled:
         out = raw2rgb.postprocess(burst.get("rawpy_image", None), out, pp.do_color_correction, pp.do_tonemapping,
@@ -990,27 +927,43 @@ def process(burst_path, config):
     else:
         out = apply_orientation(out, ori)
     acc_oriented = apply_orientation(debug_dict["accumulated robustness"], ori) if "accumulated robustness" in debug_dict else None
-    if out_dtype == "float32":
+    channels = 1 if config.mode == "grey" else None
+    if output.dtype == "float32":
         output_image = out.cpu().numpy()
+    elif output.format == "jpeg":  # the whole file's bytes, coded on the device: a tenth of the uint8 samples cross the link
+        output_image = encode_jpeg(out, quality=output.quality, restart_mcus=output.restart_mcus, channels=channels,
+                                   subsampling=output.subsampling, huffman=output.huffman)
+    elif output.format == "png":  # the whole file's bytes again: filtered and deflate-coded on the device
+        output_image = encode_png(out, bits=16 if output.dtype == "uint16" else 8, channels=channels, filter=output.filter,
+                                  interval_bytes=output.interval_bytes)
     else:  # integer output: encoded on the device, 3 or 6 instead of 12 bytes per pixel cross the host link
-        from .utils_image import encode_image, robustness_mask
-
-        channels = 1 if config.mode == "grey" else None
-        if out_format == "jpeg":  # the whole file's bytes, coded on the device: a tenth of the uint8 samples cross the link
-            from .utils_image import encode_jpeg
-
-            output_image = encode_jpeg(out, quality=out_cfg.get("quality", 90), restart_mcus=out_cfg.get("restart_mcus", None),
-                                       channels=channels, subsampling=out_sub, huffman=out_huffman)
-        elif out_format == "png":  # the whole file's bytes again: filtered and deflate-coded on the device
-            from .utils_image import encode_png
-
-            output_image = encode_png(out, bits=16 if out_dtype == "uint16" else 8, channels=channels, filter=out_filter,
-                                      interval_bytes=out_interval)
-        else:
-            output_image = encode_image(out, out_dtype, channels=channels).cpu().numpy()
-        if acc_oriented is not None and config.robustness.save_mask:  # the reference's `.rob.png` (run_handheld.py:153-159)
-            debug_dict["robustness mask"] = robustness_mask(acc_oriented, max(1, len(raw_comp)),  # (no comparison frame: the map is 0)
-                                                            tuple(out.shape[:2])).cpu().numpy()
+        output_image = encode_image(out, output.dtype, channels=channels).cpu().numpy()
+    if output.dtype != "float32" and acc_oriented is not None and config.robustness.save_mask:  # the reference's `.rob.png`
+        debug_dict["robustness mask"] = robustness_mask(acc_oriented, max(1, n_comp),  # (no comparison frame: the map is 0)
+                                                        tuple(out.shape[:2])).cpu().numpy()
     if acc_oriented is not None:
         debug_dict["accumulated robustness"] = acc_oriented.cpu().numpy()
     return output_image, debug_dict
+
+
+def process(burst_path, config):
+    """process(burst_path, config) -> (float32 ndarray [sH, sW, 3], debug_dict)   (reference :203-360).
+
+    `burst_path` is either a burst held in memory / in an .npz file — a mapping with keys ``ref`` [H,W], ``comp`` [N-1,H,W],
+    ``cfa_pattern`` [2,2], ``white_balance`` [>=3], ``alpha``, ``beta`` and optionally ``iso``, ``std_curve``,
+    ``diff_curve``, ``orientation`` (EXIF 1..8), ``xyz2cam`` (3x3, DNG ColorMatrix1, for
+    ``postprocessing.do_color_correction``) — ``cfa_pattern`` / ``white_balance`` may be left out with ``mode: grey``
+    (monochrome sensors: channel 0 of the result is the image, channels 1 and 2 are NaN like the reference's); ref / comp are
+    either normalised white-balanced float RAW or integer sensor counts with ``black_levels`` and ``white_level`` (normalised
+    on the GPU like utils_dng.py:149-160), either uint16 or, with ``packing`` (a name of utils_dng.PACKINGS) and ``width``
+    (may be left out when the rows hold no padding), the packed 10/12/14-bit rows as uint8 [H, row_bytes] — or a folder of
+    .dng files (load_burst).  The optional sections are checked in this order before the burst is touched and documented
+    where they act: ``config.output`` (output_options, finish), then ``config.reference``, ``config.noise_model`` (source,
+    frames, min_tiles; estimator, seed) and ``config.white_balance`` (intake_options, merge_stage); the denoisers,
+    ``postprocessing`` and the orientation: finish."""
+    output = output_options(config)
+    intake = intake_options(burst_path, config)
+    burst = load_burst(burst_path, config)
+    out, debug_dict, n_comp = merge_stage(burst, intake, config)
+    return finish(out, debug_dict, burst, n_comp, output, config)
+

@@ -10,6 +10,14 @@ import torch
 from . import _lib
 
 
+def to_uint16(counts):
+    """Integer sensor counts, ndarray or tensor, as uint16 of the same kind; ValueError outside its range."""
+    tensor = torch.is_tensor(counts)
+    if (counts.numel() if tensor else counts.size) and (int(counts.min()) < 0 or int(counts.max()) > 65535):
+        raise ValueError("sensor counts outside the uint16 range")
+    return counts.to(torch.int32).to(torch.uint16) if tensor else counts.astype(np.uint16)
+
+
 def normalize_burst(raw, black_levels, white_level, white_balance, cfa_pattern, device=None):
     """uint16 counts [n, H, W] (or [H, W]) -> float32 GPU tensor of the same shape:
     (count - black[c]) / (white - black[c]) * wb[c] / wb[1] per CFA colour c, in the reference's float32
@@ -21,9 +29,7 @@ def normalize_burst(raw, black_levels, white_level, white_balance, cfa_pattern, 
         if arr.dtype.is_floating_point:
             raise TypeError("normalize_burst expects integer sensor counts (got %s): float data is taken as already "
                             "normalised" % arr.dtype)
-        if int(arr.min()) < 0 or int(arr.max()) > 65535:
-            raise ValueError("sensor counts outside the uint16 range")
-        arr = arr.to(torch.int32).to(torch.uint16) if hasattr(torch, "uint16") else arr
+        arr = to_uint16(arr)
     squeeze = arr.dim() == 2
     if squeeze:
         arr = arr[None]
@@ -111,20 +117,6 @@ def unpack_raw(packed, width, packing):
         p = (g[..., :G] << lb) | ((low[..., None] >> (lb * np.arange(G, dtype=np.uint32))) & ((1 << lb) - 1))
         p = p.reshape(*b.shape[:-1], -1)[..., :width]
     return p.astype(np.uint16)
-
-
-def packed_width(raw_norm, frame):
-    """Image width of a 2-D uint8 frame that config.hip.raw_norm declares packed; None for any other frame (the decision
-    of BurstPipeline._ingest and graph.HostBurstRunner).  ValueError for a packing without a usable width."""
-    if raw_norm is None or raw_norm.get("packing", None) is None or frame.dtype != torch.uint8 or frame.dim() != 2:
-        return None
-    if raw_norm.get("width", None) is None:
-        raise ValueError("config.hip.raw_norm: 'packing' needs 'width', the pixels per row of the packed frames")
-    width = int(raw_norm["width"])
-    if width <= 0 or frame.shape[1] < packed_row_bytes(width, raw_norm["packing"]):
-        raise ValueError(f"config.hip.raw_norm: 'width' {width} as {raw_norm['packing']} needs rows of "
-                         f"{packed_row_bytes(max(width, 1), raw_norm['packing'])} bytes, the frames have {frame.shape[1]}")
-    return width
 
 
 def infer_width(row_bytes, packing):

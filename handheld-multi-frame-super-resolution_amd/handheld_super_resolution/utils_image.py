@@ -3,6 +3,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .raw_frames import COUNTS, FLOAT, PACKED, check_device_frames
 
 
 class _GreyPlan:
@@ -259,37 +260,12 @@ def frame_sharpness(frames, cfa_pattern=None, packing=None, width=None):
     (any scale), uint16 [H, W] sensor counts, or with `packing` (a name of utils_dng.PACKINGS) uint8 [H, row_bytes] packed
     rows of `width` pixels (may be left out when the rows hold no padding) — read as they lie in memory, never normalised or
     copied: only the order of a burst's frames matters.  `cfa_pattern` None: a monochrome sensor (the mean of the four
-    values of a quad).  Rows may be strided (one row stride for all frames, elements of a row adjacent).  The library is
-    called in chunks of MAX_BATCH frames; a frame's score does not depend on the chunking."""
+    values of a quad).  Rows may be strided (raw_frames.check_device_frames).  The library is called in chunks of MAX_BATCH
+    frames; a frame's score does not depend on the chunking."""
     frames = list(frames)
-    if not frames:
-        raise ValueError("frame_sharpness: no frame")
-    f0 = frames[0]
-    for t in frames:
-        if not (torch.is_tensor(t) and t.is_cuda):
-            raise RuntimeError("frame_sharpness expects tensors on the GPU (the HIP path has no CPU fallback)")
-        if t.dim() != 2 or t.shape != f0.shape or t.dtype != f0.dtype or t.device != f0.device or t.stride() != f0.stride():
-            raise ValueError("frame_sharpness: the frames need one 2-D shape, dtype, device and row stride")
-    if f0.stride(1) != 1 and f0.shape[1] > 1:
-        raise ValueError("frame_sharpness: the elements of a row must be adjacent in memory")
-    H, row_bytes = f0.shape[0], f0.stride(0) * f0.element_size()
-    if packing is not None:
-        from .utils_dng import _packing, infer_width
-
-        if f0.dtype != torch.uint8:
-            raise TypeError(f"frame_sharpness: packed frames are uint8 [H, row_bytes] (got {f0.dtype})")
-        fmt = _packing(packing)[0]
-        W = infer_width(f0.shape[1], packing) if width is None else int(width)
-        if W is None:
-            raise ValueError("frame_sharpness: give 'width' (the rows are longer than their pixels' bytes)")
-    elif f0.dtype == torch.float32:
-        fmt, W = 0, f0.shape[1]
-    elif f0.dtype in (torch.uint16, torch.int16):
-        fmt, W = -1, f0.shape[1]
-    else:
-        raise TypeError(f"frame_sharpness: float32, uint16 or packed uint8 frames (got {f0.dtype})")
+    H, W, row_bytes, fmt = check_device_frames("frame_sharpness", frames, (FLOAT, COUNTS, PACKED), packing, width)
     cfa = None if cfa_pattern is None else _lib.cfa_bytes(cfa_pattern)
-    dev = f0.device
+    dev = frames[0].device
     scores = torch.empty(len(frames), dtype=torch.float64, device=dev)
     nbytes = sharpness_workspace_bytes(H, W, min(len(frames), _lib.MAX_BATCH))
     work = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
