@@ -104,6 +104,11 @@ _SIGS = {
     "hhsr_png_file_head": [I, I, I, I, C.c_uint64, U8P, SZ, SZP],
     "hhsr_png_file_tail": [C.c_uint32, C.c_uint64, C.c_uint32, U8P, SZ, SZP],
     "hhsr_png_crc_combine": [C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32)],
+    "hhsr_ljpeg_parse": [P, SZ, P],
+    "hhsr_ljpeg_tables": [P, P, I, P],
+    "hhsr_ljpeg_workspace": [P, I, SZP],
+    "hhsr_ljpeg_decode": [P, SZ, P, I, P, I, P, SZ, P, I, I, I, L, L, P, P],
+    "hhsr_ljpeg_decode_host": [P, SZ, P, I, P, I, P, SZ, P, I, I, I, L, L, P],
     "hhsr_clock_probe": [P, L, P],
     "hhsr_merge_burst_chain": [PP, PP, PP, PP, I, I, I, I, I, I, I, P, P, U8P, D, I, I, P, P, P, I, I, P, I, P],
 }
@@ -119,6 +124,30 @@ MERGE_PLAN_LEN = 8  # HHSR_MERGE_PLAN_LEN: values of the record of hhsr_merge_pl
 MERGE_FAMILIES = ("generic", "tile", "x2_v1", "x2_mono", "x2", "x3")  # HHSR_MERGE_FAMILY_*: the record's [0]
 MERGE_GEOM_P2 = 1  # HHSR_MERGE_GEOM_P2: the record's [1]
 PNG_SPEC_BYTES = 768  # HHSR_PNG_SPEC_BYTES: the code lengths and block header of hhsr_png_huffman / hhsr_png_deflate
+LJPEG_OK, LJPEG_TRUNCATED, LJPEG_BAD_CODE, LJPEG_BAD_SEGMENT = 0, 1, 2, 3  # HHSR_LJPEG_*: a segment's status
+LJPEG_STATUS = ("OK", "TRUNCATED", "BAD_CODE", "BAD_SEGMENT")
+
+
+class LjpegInfo(C.Structure):
+    """hhsr_ljpeg_info: what hhsr_ljpeg_parse reads from one stream's marker segments."""
+    _fields_ = [("P", C.c_int32), ("Y", C.c_int32), ("X", C.c_int32), ("Nf", C.c_int32), ("predictor", C.c_int32),
+                ("point_transform", C.c_int32), ("table", C.c_int32 * 4), ("component_id", C.c_int32 * 4),
+                ("n_values", C.c_int32 * 4), ("bits", (C.c_uint8 * 16) * 4), ("values", (C.c_uint8 * 17) * 4),
+                ("data_offset", C.c_uint32), ("data_length", C.c_uint32)]
+
+
+class LjpegTable(C.Structure):
+    """hhsr_ljpeg_table: the decode table of one DHT (hhsr_ljpeg_tables)."""
+    _fields_ = [("lookup", C.c_uint16 * 256), ("maxcode", C.c_int32 * 18), ("valoff", C.c_int32 * 17),
+                ("values", C.c_uint8 * 17), ("reserved", C.c_uint8 * 3)]
+
+
+class LjpegSegment(C.Structure):
+    """hhsr_ljpeg_segment: one stream of hhsr_ljpeg_decode and where its samples go."""
+    _fields_ = [("offset", C.c_uint64), ("length", C.c_uint32), ("line_offset", C.c_uint32), ("X", C.c_int32),
+                ("Y", C.c_int32), ("Nf", C.c_int32), ("P", C.c_int32), ("predictor", C.c_int32), ("table", C.c_int32 * 4),
+                ("frame", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("seg_w", C.c_int32), ("seg_h", C.c_int32)]
+
 
 _lib = None
 

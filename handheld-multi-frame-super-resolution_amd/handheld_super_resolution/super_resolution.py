@@ -790,13 +790,36 @@ def intake_options(burst_path, config):
     return intake
 
 
+DNG_READERS = ("rawpy", "native")
+
+
+def dng_options(config):
+    """The reader of a folder of .dng files: the optional section config.dng = {"reader": "rawpy" | "native"} (not in the
+    reference schema, like config.output; absent: "rawpy").  ValueError for anything else."""
+    reader = str((config.get("dng", None) or {}).get("reader", "rawpy"))
+    if reader not in DNG_READERS:
+        raise ValueError(f"config.dng.reader {reader!r}: rawpy or native")
+    return reader
+
+
 def load_burst(burst_path, config):
     """The burst mapping of process(): `burst_path` itself, the arrays of an .npz file, or a folder of .dng files, which
     needs rawpy + exifread like the reference (absent from this image: ImportError) and takes the noise profile, ISO,
-    orientation and colour matrix from the tags of file 0.  ``mode: grey``: ``cfa_pattern`` / ``white_balance`` are filled in."""
+    orientation and colour matrix from the tags of file 0 — or, with ``config.dng.reader: native`` (dng_options, checked
+    before the burst is touched), is read by dng.read_dng_burst with the standard library and the GPU alone; a file without
+    NoiseProfile then needs ``noise_model.source: estimate``.  ``mode: grey``: ``cfa_pattern`` / ``white_balance`` are
+    filled in."""
+    reader = dng_options(config)
     burst = burst_path
     if isinstance(burst_path, (str, os.PathLike)) and str(burst_path).endswith(".npz"):
         burst = dict(np.load(burst_path))
+    elif isinstance(burst_path, (str, os.PathLike)) and reader == "native":
+        from .dng import read_dng_burst
+
+        burst = read_dng_burst(burst_path, mode=config.mode)
+        if "alpha" not in burst and noise_options(config)[0] != "estimate" and config.noise_model.get("alpha", None) is None:
+            raise ValueError(f"{burst['debug']['infos'][0].path}: NoiseProfile (50761) is missing: set "
+                             "noise_model.source: estimate to measure the noise profile from the frames")
     elif isinstance(burst_path, (str, os.PathLike)):
         ref_raw, raw_comp, iso, tags, cfa, _, white_balance, _ = load_dng_burst(burst_path)  # needs rawpy + exifread
         nm = tags["Image Tag 0xC761"].values  # DNG NoiseProfile, already scaled for the ISO (reference :232-238)

@@ -1,6 +1,8 @@
 """Burst front end (reference utils_dng.py:50-164): sensor counts -> normalised, white-balanced
-float32 RAW on the GPU.  DNG *decoding* needs rawpy + exifread like the reference; bursts that are already in
-memory (or in an .npz file) as integer arrays + metadata take the same normalisation without them — as uint16 counts, or
+float32 RAW on the GPU.  DNG *decoding* in load_dng_burst needs rawpy + exifread like the reference; dng.py reads a folder
+of .dng files without them (``config.dng.reader: native``: the container with the standard library, lossless-JPEG tiles on
+the GPU) and ends in the functions below.  Bursts that are already in
+memory (or in an .npz file) as integer arrays + metadata take the same normalisation without either — as uint16 counts, or
 as the 10/12/14-bit packed bytes the sensor interface (MIPI CSI-2) or an uncompressed DNG holds, unpacked on the GPU."""
 import ctypes
 

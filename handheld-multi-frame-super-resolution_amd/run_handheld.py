@@ -2,7 +2,8 @@
 
     python run_handheld.py --impath burst.npz --outpath out.png [--config my.yaml] [key=value ...]
 
---impath   a burst in an .npz file (the keys process() documents), or a folder of .dng files where rawpy + exifread exist
+--impath   a burst in an .npz file (the keys process() documents), or a folder of .dng files: where rawpy + exifread exist,
+           or with the override dng.reader=native read by this package itself (handheld_super_resolution/dng.py)
 --outpath  .png: 8-bit PNG;  .tif / .tiff: 16-bit uncompressed TIFF (post-processing as configured);  .dng: not built —
            the reference's DNG export runs exiftool and dng_validate on such a TIFF
 --config   a YAML file merged over the defaults (config.DEFAULTS)

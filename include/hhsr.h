@@ -949,6 +949,103 @@ int hhsr_png_file_tail(uint32_t deflate_crc, uint64_t deflate_len, uint32_t adle
                        size_t* length);
 int hhsr_png_crc_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b, uint32_t* crc);
 
+/* ---- DNG input: lossless JPEG (DNG Compression 7; ITU-T T.81 Annex H, SOF3) ----------------------------------------------
+ * No counterpart in the reference, whose frames rawpy / LibRaw decode on one CPU core before anything is uploaded.  Each
+ * tile or strip of a DNG is one independent stream: SOI, marker segments, one scan, EOI.  Python's dng.py parses the
+ * container and drives the five entry points below; csrc/hhsr_ljpeg_core.h is the one implementation of the stream rules,
+ * compiled for the host and for the kernel.
+ *
+ * hhsr_ljpeg_parse (host only, no HIP call): the stream's bytes -> *info.  Marker segments are walked by their lengths,
+ *   each inside the stream.  SOF3: P (2..16), Y, X (>= 1), Nf (1..4), per component H = V = 1 and distinct ids.  DHT: class 0,
+ *   id 0..3, 1..17 values each <= 16, code lengths with Kraft sum <= 1; bits[id] / values[id] / n_values[id] hold them.
+ *   SOS: all Nf components in frame order, table[c] the DHT id of component c (it must be present), predictor 1..7.
+ *   data_offset / data_length: the entropy-coded bytes, from behind SOS to the first marker (FF followed by a byte
+ *   other than 00) or the stream's end.  Refused, error -1, hhsr_last_error() naming it: a restart interval (DRI != 0) or
+ *   restart marker, a point transform != 0, a second scan (or a scan that holds fewer than Nf components), any SOF other
+ *   than SOF3, DAC, and every violation of the above.  APPn, COM and other segments are skipped by their length.
+ * hhsr_ljpeg_tables (host only): n (bits[16], values[17]) pairs, bits at bits + 16 i and values at values + 17 i -> the
+ *   decode tables out[i] (HOST): lookup[b] for the next HHSR_LJPEG_LOOKUP_BITS bits b of the stream is len << 8 | SSSS of
+ *   the code of len <= 8 bits that b starts with, 0 when there is none; then the ladder of T.81 F.2.2.3 for len 9..16:
+ *   the first len with (next len bits) <= maxcode[len] decodes to values[(next len bits) + valoff[len]].  maxcode[len] is
+ *   -1 where no code has that length.  Error -1 for lengths that are no prefix code, no value, more than 17, a value > 16.
+ * hhsr_ljpeg_workspace (host only): sets segs[i].line_offset of the n HOST descriptors — the line buffers one after the
+ *   other, X Nf uint16 each — and *bytes to their total.  Error -1 for X outside 1..65535, Nf outside 1..4, a total of
+ *   2^32 elements or more.
+ * hhsr_ljpeg_decode: one launch decodes the n_segs streams into out, uint16 [n_frames][H][W] with rows row_elems and frames
+ *   frame_elems ELEMENTS apart (row_elems >= W, frame_elems >= H row_elems: error -1 otherwise; they are pitches, so
+ *   nothing between the rows is written).  blob: the streams' entropy-coded bytes, 4-byte aligned, blob_bytes a multiple
+ *   of 4 (pad with anything).  Segment i: bytes blob[offset .. offset + length); X samples per line per component, Y
+ *   lines, Nf interleaved components, precision P, the scan's predictor, table[c] an index into tables[0 .. n_tables);
+ *   it belongs to frame `frame` and covers the rectangle seg_w x seg_h at (x0, y0) — a tile, or a strip of the whole width.
+ *     - Bits are taken most significant first; FF 00 is the data byte FF; FF followed by anything else, or the end of the
+ *       segment's bytes, ends the data: behind it the reader supplies zero bits, and a segment that consumed one has
+ *       status HHSR_LJPEG_TRUNCATED.  The dwords that hold the segment's first and last byte are read whole (they may
+ *       hold a neighbour's bytes, never bytes outside the blob).
+ *     - Each of the X Y Nf samples: a Huffman code gives SSSS; no code of up to 16 bits in the table ends the segment with
+ *       HHSR_LJPEG_BAD_CODE (what was stored before stays).  SSSS = 0: difference 0; 16: 32768, no further bits;
+ *       otherwise the next SSSS bits v, v - 2^SSSS + 1 when v < 2^(SSSS-1).  sample = (prediction + difference) mod 2^16.
+ *     - Prediction, per component, from Ra (left), Rb (above), Rc (above left) in the JPEG's own X x Y geometry:
+ *       2^(P-1) for the first sample, Ra on the rest of the first line, Rb in the first column, else predictor 1 Ra, 2 Rb,
+ *       3 Rc, 4 Ra+Rb-Rc, 5 Ra+((Rb-Rc)>>1), 6 Rb+((Ra-Rc)>>1), 7 (Ra+Rb)>>1.  The line above lives in
+ *       workspace[line_offset .. line_offset + X Nf), not in out.
+ *     - Sample k of the stream (line by line, components interleaved) goes FLAT into the segment: row k / seg_w, column
+ *       k % seg_w, as LibRaw and dcraw place it — so a 256-wide CFA tile coded as X = 128, Nf = 2 lands as it should.
+ *       It is stored at out[frame][y0 + row][x0 + column] when row < seg_h and the position is inside H x W; every other
+ *       sample is decoded and not stored.
+ *     - status[i] (DEVICE int32[n_segs]): HHSR_LJPEG_OK, _TRUNCATED, _BAD_CODE, or _BAD_SEGMENT for a descriptor that is
+ *       refused before anything is read or written: X or Y outside 1..65535, Nf outside 1..4, X Y Nf > 2^28, P outside
+ *       2..16, predictor outside 1..7, bytes outside the blob, frame outside 0..n_frames-1, x0 or y0 < 0, seg_w or seg_h
+ *       < 1, a line buffer outside the workspace, a table index outside 0..n_tables-1.
+ *   The loop count X Y Nf is fixed before decoding; no input makes a segment read or write outside the ranges above.  One
+ *   lane decodes one segment (Huffman decoding is serial within a stream); with up to HHSR_LJPEG_LDS_TABLES tables they
+ *   are staged in LDS once per workgroup.  No host synchronisation: the call only enqueues on `stream` and can be captured.
+ *   Error -1: a null pointer, n_segs, n_tables, n_frames, H or W <= 0, blob misaligned or blob_bytes % 4 != 0, workspace
+ *   or out misaligned for uint16, the pitches above.
+ * hhsr_ljpeg_decode_host: the same arguments, every pointer HOST memory, the same per-segment function in a plain loop on
+ *   the calling thread; no HIP call, no stream. */
+#define HHSR_LJPEG_OK 0
+#define HHSR_LJPEG_TRUNCATED 1
+#define HHSR_LJPEG_BAD_CODE 2
+#define HHSR_LJPEG_BAD_SEGMENT 3
+#define HHSR_LJPEG_MAX_COMPONENTS 4
+#define HHSR_LJPEG_LOOKUP_BITS 8
+#define HHSR_LJPEG_LDS_TABLES 16
+typedef struct hhsr_ljpeg_info {
+    int32_t P, Y, X, Nf, predictor, point_transform;
+    int32_t table[4];         /* DHT id of component c */
+    int32_t component_id[4];
+    int32_t n_values[4];      /* per DHT id; 0: not present */
+    uint8_t bits[4][16];
+    uint8_t values[4][17];
+    uint32_t data_offset, data_length;
+} hhsr_ljpeg_info;
+typedef struct hhsr_ljpeg_table {
+    uint16_t lookup[1 << HHSR_LJPEG_LOOKUP_BITS];
+    int32_t maxcode[18];
+    int32_t valoff[17];
+    uint8_t values[17];
+    uint8_t reserved[3];
+} hhsr_ljpeg_table;
+typedef struct hhsr_ljpeg_segment {
+    uint64_t offset;
+    uint32_t length;
+    uint32_t line_offset;     /* uint16 elements into the workspace: hhsr_ljpeg_workspace sets it */
+    int32_t X, Y, Nf, P, predictor;
+    int32_t table[4];
+    int32_t frame, x0, y0, seg_w, seg_h;
+} hhsr_ljpeg_segment;
+int hhsr_ljpeg_parse(const uint8_t* stream_bytes, size_t n_bytes, hhsr_ljpeg_info* info);
+int hhsr_ljpeg_tables(const uint8_t* bits, const uint8_t* values, int n, hhsr_ljpeg_table* out);
+int hhsr_ljpeg_workspace(hhsr_ljpeg_segment* segs, int n, size_t* bytes);
+int hhsr_ljpeg_decode(const uint8_t* blob, size_t blob_bytes, const hhsr_ljpeg_segment* segs, int n_segs,
+                      const hhsr_ljpeg_table* tables, int n_tables, uint16_t* workspace, size_t workspace_bytes,
+                      uint16_t* out, int n_frames, int H, int W, int64_t row_elems, int64_t frame_elems, int32_t* status,
+                      void* stream);
+int hhsr_ljpeg_decode_host(const uint8_t* blob, size_t blob_bytes, const hhsr_ljpeg_segment* segs, int n_segs,
+                           const hhsr_ljpeg_table* tables, int n_tables, uint16_t* workspace, size_t workspace_bytes,
+                           uint16_t* out, int n_frames, int H, int W, int64_t row_elems, int64_t frame_elems,
+                           int32_t* status);
+
 /* ---- measurement support ------------------------------------------------------------------------------------------
  * Shader-clock probe: one wave that sleeps for `ticks_100mhz` ticks of the constant 100 MHz counter and stores
  * {shader cycles, 100 MHz ticks} at its start and end into out4 (DEVICE uint64[4]); launched on a side stream around a
