@@ -38,6 +38,7 @@ SOURCES = {
     "hhsr_jpeg.hip": ["-ffp-contract=off"],     # the sample rule above, then the DCT and rint(c / Q): stated without contraction
     "hhsr_png.hip": ["-ffp-contract=off"],      # the same sample rule; everything behind it is integer
     "hhsr_ljpeg.hip": [],                       # DNG input: lossless JPEG decode, integer only (hhsr_ljpeg_core.h)
+    "hhsr_ljpeg_enc.hip": [],                   # DNG output: lossless JPEG encode, integer only (hhsr_ljpeg_enc_core.h)
 }
 
 
@@ -50,7 +51,7 @@ def _stale(target, deps):
 
 def build(force=False, verbose=True):
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, "hhsr_common.h"), os.path.join(CSRC, "hhsr_fft.h"), os.path.join(CSRC, "hhsr_fft_bfly.h"), os.path.join(CSRC, "hhsr_merge.h"), os.path.join(CSRC, "hhsr_jpeg_tables.h"), os.path.join(CSRC, "hhsr_png_tables.h"), os.path.join(CSRC, "hhsr_scan.h"), os.path.join(CSRC, "hhsr_ljpeg_core.h"), os.path.join(HERE, "..", "include", "hhsr.h"), __file__]
+    headers = [os.path.join(CSRC, "hhsr_common.h"), os.path.join(CSRC, "hhsr_fft.h"), os.path.join(CSRC, "hhsr_fft_bfly.h"), os.path.join(CSRC, "hhsr_merge.h"), os.path.join(CSRC, "hhsr_jpeg_tables.h"), os.path.join(CSRC, "hhsr_png_tables.h"), os.path.join(CSRC, "hhsr_scan.h"), os.path.join(CSRC, "hhsr_ljpeg_core.h"), os.path.join(CSRC, "hhsr_ljpeg_enc_core.h"), os.path.join(HERE, "..", "include", "hhsr.h"), __file__]
     jobs = []
     objs = []
     for src, extra in SOURCES.items():

@@ -109,6 +109,11 @@ _SIGS = {
     "hhsr_ljpeg_workspace": [P, I, SZP],
     "hhsr_ljpeg_decode": [P, SZ, P, I, P, I, P, SZ, P, I, I, I, L, L, P, P],
     "hhsr_ljpeg_decode_host": [P, SZ, P, I, P, I, P, SZ, P, I, I, I, L, L, P],
+    "hhsr_ljpeg_encode_workspace": [I, I, I, I, I, SZP, SZP],
+    "hhsr_ljpeg_histogram": [P, I, I, I, L, I, I, I, I, P, P, P, SZ, P],
+    "hhsr_ljpeg_huffman": [P, P, P, C.POINTER(C.c_int)],
+    "hhsr_ljpeg_encode": [P, I, I, I, L, I, I, I, I, P, P, P, SZ, P, SZ, P, P, P, P],
+    "hhsr_ljpeg_encode_host": [P, I, I, I, L, I, I, I, I, P, P, P, SZ, P, P, P],
     "hhsr_clock_probe": [P, L, P],
     "hhsr_merge_burst_chain": [PP, PP, PP, PP, I, I, I, I, I, I, I, P, P, U8P, D, I, I, P, P, P, I, I, P, I, P],
 }
@@ -126,6 +131,7 @@ MERGE_GEOM_P2 = 1  # HHSR_MERGE_GEOM_P2: the record's [1]
 PNG_SPEC_BYTES = 768  # HHSR_PNG_SPEC_BYTES: the code lengths and block header of hhsr_png_huffman / hhsr_png_deflate
 LJPEG_OK, LJPEG_TRUNCATED, LJPEG_BAD_CODE, LJPEG_BAD_SEGMENT = 0, 1, 2, 3  # HHSR_LJPEG_*: a segment's status
 LJPEG_STATUS = ("OK", "TRUNCATED", "BAD_CODE", "BAD_SEGMENT")
+LJPEG_BAD_SAMPLE = 4  # HHSR_LJPEG_BAD_SAMPLE: hhsr_ljpeg_histogram's status for a sample at or above 2^P
 
 
 class LjpegInfo(C.Structure):

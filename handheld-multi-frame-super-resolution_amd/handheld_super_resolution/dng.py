@@ -467,3 +467,97 @@ def read_dng_burst(folder, device=None, decoder="host", mode="bayer"):
         else:
             burst.update(alpha=sum(nm[0:6:2]) / 3, beta=sum(nm[1:6:2]) / 3)
     return burst
+
+
+# ---- DNG output: the container --------------------------------------------------------------------------------------------
+
+XYZ_TO_SRGB_D65 = ((3.2404542, -1.5371385, -0.4985314), (-0.9692660, 1.8760108, 0.0415560), (0.0556434, -0.2040259, 1.0572252))
+DEFAULT_CAMERA_MODEL = "handheld super-resolution"  # UniqueCameraModel of a burst that names no camera
+_RATIONAL_DEN = 1000000
+
+
+def _rational(x, signed):
+    """(numerator, denominator) of x rounded to 10^-6; what does not fit 32 bits is a ValueError."""
+    n = int(round(float(x) * _RATIONAL_DEN))
+    if not (-(1 << 31) <= n < (1 << 31) if signed else 0 <= n < (1 << 32)):
+        raise ValueError(f"dng_head: {x!r} does not fit a {'signed ' if signed else ''}rational with denominator {_RATIONAL_DEN}")
+    return n, _RATIONAL_DEN
+
+
+def dng_head(height, width, samples, tile_h, tile_w, tile_offsets=None, tile_byte_counts=None, *, orientation=1,
+             camera_model=None, xyz2cam=None, white_balance=None, calibration_illuminant=None):
+    """The bytes in front of the tile streams of a LinearRaw DNG (utils_dng.encode_dng): the classic little-endian TIFF
+    header, IFD0 and the values it points at.  The file is ``head || streams`` with TileOffsets[i] = len(head) +
+    `tile_offsets[i]`; the head's length depends only on the number of tiles and on `samples` and `camera_model`, so it is known
+    before anything is coded (`tile_offsets` / `tile_byte_counts` None: zeros).  It is even, every value offset is even, the
+    entries are in ascending tag order.
+
+    IFD0: NewSubFileType 0, ImageWidth / ImageLength, BitsPerSample 16 per sample, Compression 7, PhotometricInterpretation
+    34892 (LinearRaw), Orientation, SamplesPerPixel `samples` (1 or 3), PlanarConfiguration 1, TileWidth / TileLength /
+    TileOffsets / TileByteCounts, DNGVersion 1.4.0.0, DNGBackwardVersion 1.1.0.0, UniqueCameraModel, BlackLevel 0 and
+    WhiteLevel 65535 per sample, BaselineExposure 0; with three samples also ColorMatrix1 (`xyz2cam`; None: XYZ -> linear
+    sRGB, D65), AnalogBalance (`white_balance` normalised to green; None: 1 1 1), AsShotNeutral 1 1 1 and
+    CalibrationIlluminant1 (None: 21, D65).  The frames were multiplied by the white balance before the merge, so the data's
+    camera space is diag(wb) ColorMatrix: AnalogBalance says exactly that (upstream's choice).  No preview IFD, no XMP, no
+    NoiseProfile."""
+    H, W, spp, th, tw = int(height), int(width), int(samples), int(tile_h), int(tile_w)
+    if spp not in (1, 3):
+        raise ValueError(f"dng_head: samples={samples!r}: 1 or 3")
+    if H < 1 or W < 1 or th < 1 or tw < 1:
+        raise ValueError(f"dng_head: {H} x {W} in tiles of {th} x {tw}")
+    if not 1 <= int(orientation) <= 8:
+        raise ValueError(f"dng_head: orientation={orientation!r}: 1 .. 8")
+    n = (-(-H // th)) * (-(-W // tw))
+    offs = [0] * n if tile_offsets is None else [int(v) for v in tile_offsets]
+    cnts = [0] * n if tile_byte_counts is None else [int(v) for v in tile_byte_counts]
+    if len(offs) != n or len(cnts) != n:
+        raise ValueError(f"dng_head: {len(offs)} offsets and {len(cnts)} byte counts for {n} tiles")
+    model = (DEFAULT_CAMERA_MODEL if camera_model is None else str(camera_model)).encode("ascii", "replace") + b"\0"
+    BYTE, ASCII, SHORT, LONG, RATIONAL, SRATIONAL = 1, 2, 3, 4, 5, 10
+    entries = [(254, LONG, [0]), (256, LONG, [W]), (257, LONG, [H]), (258, SHORT, [16] * spp), (259, SHORT, [7]),
+               (262, SHORT, [34892]), (274, SHORT, [int(orientation)]), (277, SHORT, [spp]), (284, SHORT, [1]),
+               (322, LONG, [tw]), (323, LONG, [th]), (324, LONG, None), (325, LONG, cnts),
+               (50706, BYTE, [1, 4, 0, 0]), (50707, BYTE, [1, 1, 0, 0]), (50708, ASCII, model),
+               (50714, SHORT, [0] * spp), (50717, LONG, [65535] * spp)]
+    if spp == 3:
+        cm = np.asarray(XYZ_TO_SRGB_D65 if xyz2cam is None else xyz2cam, np.float64).reshape(-1)
+        if cm.size != 9 or not np.isfinite(cm).all():
+            raise ValueError("dng_head: xyz2cam is no finite 3 x 3 matrix")
+        wb = [1.0, 1.0, 1.0] if white_balance is None else [float(v) for v in np.asarray(white_balance).reshape(-1)[:3]]
+        if len(wb) != 3 or not all(np.isfinite(v) and v > 0 for v in wb):
+            raise ValueError(f"dng_head: white_balance={white_balance!r}: three positive values")
+        illuminant = 21 if calibration_illuminant is None else int(calibration_illuminant)
+        entries += [(50721, SRATIONAL, [_rational(v, True) for v in cm]),
+                    (50727, RATIONAL, [_rational(v / wb[1], False) for v in wb]),
+                    (50728, RATIONAL, [(1, 1)] * 3)]
+    entries.append((50730, SRATIONAL, [(0, 1)]))
+    if spp == 3:
+        entries.append((50778, SHORT, [illuminant]))
+
+    def payload(typ, vals):
+        if typ == ASCII:
+            return bytes(vals)
+        if typ in (RATIONAL, SRATIONAL):
+            return b"".join(struct.pack("<II" if typ == RATIONAL else "<ii", a, b) for a, b in vals)
+        return struct.pack("<" + str(len(vals)) + {BYTE: "B", SHORT: "H", LONG: "I"}[typ], *vals)
+
+    ifd_at = 8
+    values_at = ifd_at + 2 + 12 * len(entries) + 4  # even: 8 + 2 + 12 k + 4
+    # two passes: the first lays the values out (TileOffsets needs the head's length), the second writes them
+    head_len = None
+    for _ in range(2):
+        body, table = b"", b""
+        for tag, typ, vals in entries:
+            if tag == 324:
+                vals = [(head_len or 0) + o for o in offs]
+                if head_len is not None and vals and max(vals) + max(cnts) >= 1 << 32:
+                    raise ValueError("dng_head: the file passes 4 GiB (BigTIFF is not written)")
+            data = payload(typ, vals)
+            if len(data) <= 4:
+                field = data + b"\0" * (4 - len(data))
+            else:
+                field = struct.pack("<I", values_at + len(body))
+                body += data + (b"\0" if len(data) & 1 else b"")  # every value starts at an even offset
+            table += struct.pack("<HHI", tag, typ, len(vals)) + field
+        head_len = values_at + len(body)
+    return b"II*\0" + struct.pack("<I", ifd_at) + struct.pack("<H", len(entries)) + table + struct.pack("<I", 0) + body

@@ -27,7 +27,7 @@ from . import _lib, raw2rgb
 from .config import hip_opt, positive_int
 from .noise_profile import estimate_noise_profile, noise_options
 from .raw_frames import FLOAT, RawLayout, host_counts
-from .utils_dng import load_dng_burst
+from .utils_dng import dng_option, encode_dng, load_dng_burst
 from .utils_image import (apply_orientation, compute_grey_images, compute_grey_images_batch, encode_image, encode_jpeg,
                           encode_png, frame_count_denoising_gauss, frame_count_denoising_median, frame_sharpness,
                           jpeg_option, png_option, robustness_mask)
@@ -725,8 +725,8 @@ def prepare_config(config, ref_raw, alpha=None, beta=None, cfa_pattern=None, whi
     return config
 
 
-OutputOptions = namedtuple("OutputOptions", "format dtype quality restart_mcus subsampling huffman filter interval_bytes",
-                           defaults=(None,) * 6)
+OutputOptions = namedtuple("OutputOptions", "format dtype quality restart_mcus subsampling huffman filter interval_bytes "
+                                            "tile predictor", defaults=(None,) * 8)
 IntakeOptions = namedtuple("IntakeOptions", "ref_select noise_source noise_frames noise_min_tiles wb_source wb_frames wb_min_tiles")
 
 
@@ -748,9 +748,24 @@ def output_options(config):
     the complete PNG file of the uint8 (default) or uint16 image as a 1-D uint8 ndarray, filtered and deflate-coded on the
     GPU (utils_image.encode_png; colour type 0 with ``mode: grey``; write it with utils_image.save_png_bytes).  ``filter``:
     none | sub | up | average | paeth | adaptive (default); ``interval_bytes``: 1 .. 2^20 (default
-    utils_image.PNG_INTERVAL_BYTES).  ``dtype: float32``, another filter name or interval is a ValueError."""
+    utils_image.PNG_INTERVAL_BYTES).  ``dtype: float32``, another filter name or interval is a ValueError.
+    ``config.output = {"format": "dng", "tile": ..., "predictor": ...}``: the result is the complete LinearRaw DNG file of the
+    uint16 image as a 1-D uint8 ndarray, its lossless-JPEG tiles coded on the GPU (utils_dng.encode_dng; one sample per
+    pixel with ``mode: grey``; write it with utils_dng.save_dng_bytes).  ``tile``: one integer or [h, w], multiples of 16 in
+    16 .. 65535 (default utils_dng.DNG_TILE); ``predictor``: 1 .. 7 (default 1); ``dtype`` may be absent or "uint16".  A DNG
+    holds the linear image: ``postprocessing.enabled: true`` with it is a ValueError, and the image is not rotated — the
+    burst's orientation goes into the file's Orientation tag (finish)."""
     sec = config.get("output", None) or {}
     fmt = str(sec.get("format", "raw"))
+    if fmt == "dng":
+        dtype = str(sec.get("dtype", "uint16"))
+        if dtype != "uint16":
+            raise ValueError(f"config.output.format dng holds 16-bit samples: output.dtype {dtype!r} contradicts it")
+        tile, predictor = dng_option("tile", _plain(sec.get("tile", None))), dng_option("predictor", sec.get("predictor", None))
+        if config.postprocessing.enabled:
+            raise ValueError("config.output.format dng holds the linear image: switch post-processing off "
+                             "(postprocessing.enabled: false)")
+        return OutputOptions(fmt, dtype, tile=tile, predictor=predictor)
     if fmt not in ("raw", "jpeg", "png"):
         raise ValueError(f"config.output.format {fmt!r}: raw, jpeg or png")
     dtype = str(sec.get("dtype", "uint8" if fmt in ("jpeg", "png") else "float32"))
@@ -774,6 +789,11 @@ def output_options(config):
         return OutputOptions(fmt, dtype, filter=png_option("filter", sec.get("filter", "adaptive")),
                              interval_bytes=png_option("interval_bytes", sec.get("interval_bytes", None)))
     return OutputOptions(fmt, dtype)
+
+
+def _plain(value):
+    """A list node of the configuration as a plain list (scalars and None pass)."""
+    return list(value) if hasattr(value, "__len__") and not isinstance(value, (str, bytes)) else value
 
 
 def intake_options(burst_path, config):
@@ -934,7 +954,9 @@ def finish(out, debug_dict, burst, n_comp, output, config):
     raw2rgb.postprocess with restated_tonemapping=True) and the EXIF orientation, then what `output` (output_options) asks
     for.  With an integer dtype and ``robustness.save_mask``, ``debug_dict["robustness mask"]`` is the reference's mask
     image: uint8 [sH, sW], accumulated robustness / number of comparison frames, nearest neighbour (hhsr_encode_mask); it
-    stays that uint8 array with ``format: jpeg`` and ``png``."""
+    stays that uint8 array with ``format: jpeg``, ``png`` and ``dng``.  ``format: dng`` keeps the linear image: the
+    denoisers run, post-processing is off (output_options) and the image is NOT rotated — the orientation becomes the file's
+    Orientation tag; the mask and ``debug_dict["accumulated robustness"]`` are oriented as for the other formats."""
     den = config.accumulated_robustness_denoiser
     half_index = bool((config.get("compat", None) or {}).get("post_denoiser_half_index", True))
     for stage, denoise in ((den.median, frame_count_denoising_median), (den.gauss, frame_count_denoising_gauss)):
@@ -943,11 +965,12 @@ def finish(out, debug_dict, burst, n_comp, output, config):
                           mode=config.mode)
     ori = int(burst.get("orientation", 1))  # EXIF 'Image Orientation' (reference :346-352)
     pp = config.postprocessing
-    if pp.enabled:
+    dng = output.format == "dng"  # the linear image as it was merged: the orientation goes into the file's tag
+    if pp.enabled and not dng:
         out = raw2rgb.postprocess(burst.get("rawpy_image", None), out, pp.do_color_correction, pp.do_tonemapping,
                                   pp.do_gamma_correction, pp.sharpening, pp.do_devignetting, burst.get("xyz2cam", None),
                                   orientation=ori, restated_tonemapping=True)
-    else:
+    elif not dng:
         out = apply_orientation(out, ori)
     acc_oriented = apply_orientation(debug_dict["accumulated robustness"], ori) if "accumulated robustness" in debug_dict else None
     channels = 1 if config.mode == "grey" else None
@@ -959,11 +982,18 @@ def finish(out, debug_dict, burst, n_comp, output, config):
     elif output.format == "png":  # the whole file's bytes again: filtered and deflate-coded on the device
         output_image = encode_png(out, bits=16 if output.dtype == "uint16" else 8, channels=channels, filter=output.filter,
                                   interval_bytes=output.interval_bytes)
+    elif dng:  # a LinearRaw DNG: lossless-JPEG tiles coded on the device, the file's bytes cross the link
+        wb = burst.get("white_balance", None)
+        output_image = encode_dng(out, channels=channels, tile=output.tile, predictor=output.predictor,
+                                  xyz2cam=burst.get("xyz2cam", None), white_balance=None if wb is None else np.asarray(wb),
+                                  orientation=ori, camera_model=burst.get("camera_model", None),
+                                  calibration_illuminant=burst.get("calibration_illuminant", None))
     else:  # integer output: encoded on the device, 3 or 6 instead of 12 bytes per pixel cross the host link
         output_image = encode_image(out, output.dtype, channels=channels).cpu().numpy()
     if output.dtype != "float32" and acc_oriented is not None and config.robustness.save_mask:  # the reference's `.rob.png`
+        mask_shape = tuple(out.shape[:2])[::-1] if dng and ori >= 5 else tuple(out.shape[:2])  # (the mask is oriented)
         debug_dict["robustness mask"] = robustness_mask(acc_oriented, max(1, n_comp),  # (no comparison frame: the map is 0)
-                                                        tuple(out.shape[:2])).cpu().numpy()
+                                                        mask_shape).cpu().numpy()
     if acc_oriented is not None:
         debug_dict["accumulated robustness"] = acc_oriented.cpu().numpy()
     return output_image, debug_dict

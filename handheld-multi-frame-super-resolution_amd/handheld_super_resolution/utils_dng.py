@@ -203,7 +203,7 @@ def save_as_tiff(int_im, outpath):
     """uint8 / uint16 ndarray [H, W] or [H, W, 3] -> baseline TIFF (reference utils_dng.py:327-341, which writes it through
     imageio with bigtiff=False): little-endian, uncompressed, one strip, chunky, standard library only.  A path that does
     not end in .tif / .tiff gets the suffix .tif, as upstream.  RuntimeError when the file would pass classic TIFF's 4 GiB,
-    like the reference.  save_as_dng is not part of this build: it needs exiftool and dng_validate."""
+    like the reference."""
     import os
     import struct
 
@@ -246,3 +246,135 @@ def save_as_tiff(int_im, outpath):
 def _tiff_pixel_bytes(a):
     """Bytes of the one strip (its own function: the 4 GiB refusal is tested without allocating 4 GiB)."""
     return int(a.size) * a.dtype.itemsize
+
+
+# ---- DNG output (include/hhsr.h "DNG output: lossless JPEG"; the reference's save_as_dng runs exiftool and dng_validate) -------
+DNG_TILE = 128      # default tile edge, chosen by measurement (profiles/dng_encode.txt, 48 MP): the fastest of 128 / 256 / 512
+#                     whose file is within 1 % of the smallest of the three.  128 is both: 2961 workgroups fill the chip where
+#                     768 or 192 do not, and the replicated rows below the image, which predictor 1 codes at full cost, are fewest
+DNG_PREDICTOR = 1   # what DNG writers use; the decoder keeps it out of its switch
+
+
+def dng_option(name, value):
+    """The canonical value of an encode_dng / config.output option: tile -> (tile_h, tile_w), each a multiple of 16 in
+    16 .. 65535, from one integer or a pair (None: DNG_TILE square); predictor -> an int in 1 .. 7 (None: DNG_PREDICTOR).
+    Anything else is a ValueError."""
+    def integer(v):
+        return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+
+    if name == "tile":
+        if value is None:
+            return DNG_TILE, DNG_TILE
+        pair = [value, value] if integer(value) else list(value) if hasattr(value, "__len__") and not isinstance(value, str) else None
+        if pair is None or len(pair) != 2 or not all(integer(v) and 16 <= int(v) <= 65535 and int(v) % 16 == 0 for v in pair):
+            raise ValueError(f"tile={value!r}: one integer or [h, w], each a multiple of 16 in 16 .. 65535")
+        return int(pair[0]), int(pair[1])
+    if name == "predictor":
+        if value is None:
+            return DNG_PREDICTOR
+        if not integer(value) or not 1 <= int(value) <= 7:
+            raise ValueError(f"predictor={value!r}: an integer in 1 .. 7")
+        return int(value)
+    raise ValueError(f"dng_option: no option {name!r}")
+
+
+def ljpeg_encode_workspace(H, W, Nf, tile_h, tile_w):
+    """(bytes of the scratch, largest possible result) of hhsr_ljpeg_encode_workspace."""
+    a, b = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _lib.call("hhsr_ljpeg_encode_workspace", int(H), int(W), int(Nf), int(tile_h), int(tile_w), ctypes.byref(a), ctypes.byref(b))
+    return a.value, b.value
+
+
+def ljpeg_huffman(counts):
+    """hhsr_ljpeg_huffman per row of counts [Nf, 17] (host) -> (bits uint8 [Nf, 16], values uint8 [Nf, 17]): T.81 Annex K.2."""
+    c = np.ascontiguousarray(counts, np.uint64)
+    if c.ndim != 2 or c.shape[1] != 17 or not 1 <= c.shape[0] <= 4:
+        raise ValueError(f"ljpeg_huffman expects counts [Nf, 17], got {c.shape}")
+    bits, values, n = np.zeros((c.shape[0], 16), np.uint8), np.zeros((c.shape[0], 17), np.uint8), ctypes.c_int(0)
+    for i in range(c.shape[0]):
+        _lib.call("hhsr_ljpeg_huffman", c[i].ctypes.data, bits[i].ctypes.data, values[i].ctypes.data, ctypes.byref(n))
+    return bits, values
+
+
+def encode_dng(img, *, channels=None, tile=None, predictor=None, xyz2cam=None, white_balance=None, orientation=1,
+               camera_model=None, calibration_illuminant=None, capacity=None):
+    """Device float32 [H, W, 3] or [H, W] -> the complete LinearRaw DNG file as a 1-D uint8 ndarray: the samples of
+    encode_image(img, "uint16") in tiles of `tile` (one integer or (h, w); default DNG_TILE), each one lossless-JPEG stream
+    (Compression 7, `predictor` 1 .. 7) coded on the device with Huffman tables made for this image, behind the container of
+    dng.dng_head (which documents the tags and what `xyz2cam`, `white_balance`, `orientation`, `camera_model` and
+    `calibration_illuminant` become).  `channels=1` of an [H, W, 3] image: channel 0 alone, one sample per pixel (`mode: grey`).
+    Two synchronisations, as encode_png: the Nf x 17 category counts are copied (hhsr_ljpeg_histogram), hhsr_ljpeg_huffman
+    builds one table per component on the host, the streams are coded into `capacity` device bytes (default: the size of
+    the uncompressed samples plus 256 bytes per tile), the offsets, byte counts and the length are read, and exactly the
+    streams' bytes are copied behind the head; a result that did not fit is coded once more into a buffer of the reported
+    length."""
+    from .dng import dng_head
+    from .utils_image import encode_image
+
+    if not (torch.is_tensor(img) and img.is_cuda):
+        raise RuntimeError("encode_dng expects a tensor on the GPU (the HIP path has no CPU fallback)")
+    tile_h, tile_w = dng_option("tile", tile)
+    predictor = dng_option("predictor", predictor)
+    samples = encode_image(img, "uint16", channels=channels)  # (checks the shape; int16 storage of the uint16 samples)
+    H, W = samples.shape[:2]
+    nf = 1 if samples.dim() == 2 else samples.shape[2]
+    dev, stream = samples.device, _lib.stream(samples.device)
+    n_tiles = (-(-H // tile_h)) * (-(-W // tile_w))
+    meta = dict(orientation=orientation, camera_model=camera_model, xyz2cam=xyz2cam, white_balance=white_balance,
+                calibration_illuminant=calibration_illuminant)
+    head_len = len(dng_head(H, W, nf, tile_h, tile_w, **meta))  # (also refuses what the container cannot hold, before any launch)
+    scratch_bytes, _ = ljpeg_encode_workspace(H, W, nf, tile_h, tile_w)
+    scratch = torch.empty((scratch_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    counts = torch.empty(nf * 17 + 1, dtype=torch.int64, device=dev)  # [Nf][17], then the status word
+    args = (_lib.ptr(samples), H, W, nf, W * nf, 16, predictor, tile_h, tile_w)
+    _lib.call("hhsr_ljpeg_histogram", *args, _lib.ptr(counts), ctypes.c_void_p(counts.data_ptr() + 8 * nf * 17),
+              _lib.ptr(scratch), scratch.numel() * 8, stream)
+    bits, values = ljpeg_huffman(counts.cpu().numpy().view(np.uint64)[:nf * 17].reshape(nf, 17))  # (synchronises: the counts)
+    record = torch.empty(n_tiles + 2 + (n_tiles + 1) // 2, dtype=torch.int64, device=dev)  # offsets, length, byte counts
+    p_off = record.data_ptr()
+    p_len, p_cnt = p_off + 8 * (n_tiles + 1), p_off + 8 * (n_tiles + 2)
+    cap = H * W * nf * 2 + 256 * n_tiles if capacity is None else int(capacity)
+    for _ in range(2):  # at most one retry, with the length the first pass reported
+        out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+        _lib.call("hhsr_ljpeg_encode", *args, bits.ctypes.data, values.ctypes.data, _lib.ptr(scratch), scratch.numel() * 8,
+                  _lib.ptr(out), cap, ctypes.c_void_p(p_off), ctypes.c_void_p(p_cnt), ctypes.c_void_p(p_len), stream)
+        rec = record.cpu().numpy()  # (synchronises: 12 bytes per tile)
+        offsets = rec[:n_tiles + 1].view(np.uint64)
+        byte_counts = rec[n_tiles + 2:].view(np.uint32)[:n_tiles]
+        length = int(rec[n_tiles + 1:n_tiles + 2].view(np.uint64)[0])
+        if length == (1 << 64) - 1:  # (cannot happen with tables built from this image's counts)
+            raise RuntimeError("encode_dng: the Huffman tables lack a category the image holds")
+        if length <= cap:
+            break
+        cap = length
+    else:
+        raise RuntimeError(f"encode_dng: the streams need {length} bytes after a retry with the reported length")
+    head = dng_head(H, W, nf, tile_h, tile_w, offsets[:n_tiles], byte_counts, **meta)
+    assert len(head) == head_len
+    data = np.empty(head_len + length, np.uint8)
+    data[:head_len] = np.frombuffer(head, np.uint8)
+    torch.from_numpy(data)[head_len:].copy_(out[:length])  # (device -> its place in the file: one host copy)
+    return data
+
+
+def save_dng_bytes(file_bytes, path):
+    """The array encode_dng (or process() with output.format = dng) returned -> a file."""
+    a = np.asarray(file_bytes)
+    if a.dtype != np.uint8 or a.ndim != 1 or a.size < 8 or a[:4].tobytes() != b"II*\0":
+        raise ValueError("save_dng_bytes expects the 1-D uint8 array of encode_dng")
+    with open(path, "wb") as f:
+        f.write(a.tobytes())
+
+
+def save_as_dng(np_img, ref_dng_path, outpath):
+    """The reference's signature (utils_dng.py:218-325): the linear image `np_img` (float [H, W, 3] or [H, W], host or
+    device) as a DNG at `outpath`, with the colour matrix, white balance and orientation of `ref_dng_path` read by
+    dng.parse_dng.  Upstream writes a 16-bit TIFF and rewrites its tags with exiftool, then runs dng_validate; here the file
+    is coded on the GPU (encode_dng) and neither tool is needed."""
+    from .dng import parse_dng
+
+    info = parse_dng(ref_dng_path)
+    img = np_img if torch.is_tensor(np_img) else torch.as_tensor(np.ascontiguousarray(np_img, np.float32))
+    data = encode_dng(_lib.f32c(img), xyz2cam=info.xyz2cam, white_balance=info.white_balance,
+                      orientation=info.orientation or 1)
+    save_dng_bytes(data, outpath)

@@ -1046,6 +1046,75 @@ int hhsr_ljpeg_decode_host(const uint8_t* blob, size_t blob_bytes, const hhsr_lj
                            uint16_t* out, int n_frames, int H, int W, int64_t row_elems, int64_t frame_elems,
                            int32_t* status);
 
+/* ---- DNG output: lossless JPEG (run_handheld.py: save_as_dng for a `.dng` path, through exiftool, on the host) -------------
+ * The finished image's uint16 samples as the tiles of a DNG with Compression 7, coded on the device: what crosses the host
+ * link is the file, not its samples.  Unlike the decoder above the encoder is parallel — every prediction comes from the
+ * original samples, so the bits of every sample are independent and only their positions need a prefix sum.  Python's
+ * utils_dng.py drives the entry points below and dng.py writes the container; csrc/hhsr_ljpeg_enc_core.h is the one
+ * implementation of the per-sample rule, compiled for the host and for the kernels; tests/ljpeg_ref.py is its NumPy form.
+ *
+ *   samples      uint16 [H][W][Nf], rows row_elems ELEMENTS apart (row_elems >= W Nf; nothing between the rows is read),
+ *                2-byte aligned (4-byte aligned with an even row_elems: dword loads).  H, W 1..2^30, Nf 1..4, precision P 2..16,
+ *                predictor 1..7.  A sample at or above 2^P is reported (below), never undefined behaviour: the rules
+ *                work modulo 2^16.
+ *   tiles        tile_h x tile_w, each 16..65535 and a multiple of 16, tile_h tile_w Nf <= 2^28 (what the decoder accepts as
+ *                one stream); ceil(H / tile_h) x ceil(W / tile_w) of them in row-major order; the padded image holds at most
+ *                2^40 samples.  Tile (ty, tx) is one complete stream with X = tile_w, Y = tile_h and Nf interleaved
+ *                components of s(y, x) = image(min(ty tile_h + y, H - 1), min(tx tile_w + x, W - 1)): the edge replicates.
+ *   a sample     prediction from Ra (left), Rb (above), Rc (above left) OF THE TILE, as in "DNG input" above: 2^(P-1) for the
+ *                first sample, Ra on the first line, Rb in the first column, else the predictor's rule.  difference =
+ *                (sample - prediction) mod 2^16 as -32767 .. 32768; SSSS = the bits of its magnitude (32768: 16).  Its bits:
+ *                the code word of SSSS, then the SSSS low bits of the difference (of difference - 1 when negative), none
+ *                for SSSS 0 and 16.
+ *   a stream     SOI; SOF3 (P, Y, X, Nf, component ids 1 .. Nf with H = V = 1, Tq 0); one DHT per component, class 0, id =
+ *                the component's index, its bits[16] and values; SOS (component c uses table c; the predictor; no point
+ *                transform); the samples' bits line by line, most significant first, padded with 1-bits to a byte, every
+ *                FF followed by 00; EOI.  No restart interval.  Exactly tests/ljpeg_ref.py: encode(tile, P, predictor,
+ *                tables, comp_table = [0 .. Nf-1]).
+ *   the result   the streams one after the other, each at an even offset: offsets[i] (uint64 [n_tiles + 1]) is where stream i
+ *                starts and offsets[n_tiles] = *length the end; tile_bytes[i] (uint32 [n_tiles]) is the stream's length
+ *                from SOI to EOI.  A stream of odd length is followed by one 00 byte, which offsets[i + 1] - offsets[i]
+ *                counts and tile_bytes[i] does not.
+ *   bounds       a sample costs at most 16 code bits and 15 magnitude bits (SSSS 16 has none) and every byte of the scan may
+ *                be an FF that is stuffed: a stream holds at most  h + 2 ceil(31 tile_h tile_w Nf / 8) + 2  bytes, h =
+ *                2 + (10 + 3 Nf) + 38 Nf + (8 + 2 Nf) for SOI, SOF3, Nf DHTs of 17 values and SOS, 2 for EOI; one more for
+ *                the even offset.  max_bytes = n_tiles times that; it is below 2^32 per tile, which the offsets scan relies on.
+ *
+ * hhsr_ljpeg_encode_workspace (host only): *scratch_bytes for hhsr_ljpeg_histogram (one partial table of 72 uint64 for each
+ *   of at most 1024 workgroups) and hhsr_ljpeg_encode (4 bytes per tile + 8 per 2048 tiles), the larger; *max_bytes.
+ * hhsr_ljpeg_histogram: samples DEVICE -> counts DEVICE uint64 [Nf][17], 8-byte aligned, overwritten: how often each SSSS
+ *   occurs per component over all tiles, the replicated samples included.  Exact integers, the same for any row_elems,
+ *   alignment and order of the workgroups: LDS atomics per workgroup, one partial table each, summed by a second launch; no
+ *   atomics on device memory.  *status (DEVICE uint32): HHSR_LJPEG_OK, or HHSR_LJPEG_BAD_SAMPLE when a sample is >= 2^P.
+ *   scratch DEVICE, 8-byte aligned.  Two launches.
+ * hhsr_ljpeg_huffman (host only, HOST pointers, no HIP call): counts [17] -> bits [16], values [17] (*n_values of them, the
+ *   rest 0) by T.81 Annex K.2, figures K.1 to K.4 with the reserved code point (ties: the larger index): zero counts get
+ *   no code, no code is longer than 16 bits or all 1-bits.  Error -1 when no count is set or the sum passes 2^62.
+ * hhsr_ljpeg_encode: samples DEVICE and the HOST tables bits [Nf][16], values [Nf][17] -> out[0 .. capacity) DEVICE bytes (no
+ *   alignment), offsets, tile_bytes and *length (DEVICE; 8-, 4-, 8-byte aligned).  The code words and the streams' fixed
+ *   bytes travel as a by-value kernel argument: no copy, no allocation, the call stays capturable, the tables may be freed on
+ *   return.  A result longer than capacity is cut there — no byte outside [out, out + capacity) is written — and offsets,
+ *   tile_bytes and *length are still those of the whole result.  A category the tables give no code, or a sample >= 2^P:
+ *   *length = UINT64_MAX, the bytes unspecified.  The bytes are the same in every run and on every stream.  One workgroup
+ *   per tile walks its stream in batches of 2048 samples (csrc/hhsr_ljpeg_enc.hip).  Five launches: sizes, the offsets scan
+ *   (three), the write pass.  No host synchronisation.
+ * hhsr_ljpeg_encode_host: the same without scratch and stream, every pointer HOST memory: a plain loop on the calling thread
+ *   over the same per-sample function, no HIP call, the same bytes.
+ * All: error -1 before any HIP call for a null or misaligned pointer, dimensions, P, predictor or tile outside the above,
+ *   row_elems < W Nf, a scratch smaller than stated, overlapping buffers, tables that are no prefix code (per component
+ *   1..17 distinct values <= 16, Kraft sum <= 1). */
+#define HHSR_LJPEG_BAD_SAMPLE 4
+int hhsr_ljpeg_encode_workspace(int H, int W, int Nf, int tile_h, int tile_w, size_t* scratch_bytes, size_t* max_bytes);
+int hhsr_ljpeg_histogram(const uint16_t* samples, int H, int W, int Nf, int64_t row_elems, int P, int predictor, int tile_h,
+                         int tile_w, uint64_t* counts, uint32_t* status, void* scratch, size_t scratch_bytes, void* stream);
+int hhsr_ljpeg_huffman(const uint64_t* counts, uint8_t* bits, uint8_t* values, int* n_values);
+int hhsr_ljpeg_encode(const uint16_t* samples, int H, int W, int Nf, int64_t row_elems, int P, int predictor, int tile_h,
+                      int tile_w, const uint8_t* bits, const uint8_t* values, void* scratch, size_t scratch_bytes,
+                      uint8_t* out, size_t capacity, uint64_t* offsets, uint32_t* tile_bytes, uint64_t* length, void* stream);
+int hhsr_ljpeg_encode_host(const uint16_t* samples, int H, int W, int Nf, int64_t row_elems, int P, int predictor, int tile_h,
+                           int tile_w, const uint8_t* bits, const uint8_t* values, uint8_t* out, size_t capacity,
+                           uint64_t* offsets, uint32_t* tile_bytes, uint64_t* length);
+
 /* ---- measurement support ------------------------------------------------------------------------------------------
  * Shader-clock probe: one wave that sleeps for `ticks_100mhz` ticks of the constant 100 MHz counter and stores
  * {shader cycles, 100 MHz ticks} at its start and end into out4 (DEVICE uint64[4]); launched on a side stream around a
