@@ -30,6 +30,7 @@ SOURCES = {
     # row kernels, 94 -> 89 us of the column kernel at 12 MP x 3-4 frames — tools/ab.sh --kernels "k_rows|k_cols" slp@fft_slp default)
     "hhsr_fft.hip": ["-fno-slp-vectorize"],
     "hhsr_io.hip": ["-ffp-contract=off"],
+    "hhsr_linearize.hip": ["-ffp-contract=off"],  # DNG linearization: stated operation by operation, rounded once each (hhsr.h)
     "hhsr_post.hip": ["-ffp-contract=off"],
     "hhsr_tonemap.hip": ["-ffp-contract=off"],  # the Mertens weight maps are a decision stage (exact float32 association)
     "hhsr_noise.hip": ["-ffp-contract=off"],    # the Monte-Carlo stream is stated without fused multiply-adds (hhsr.h)

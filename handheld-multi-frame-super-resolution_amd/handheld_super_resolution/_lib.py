@@ -51,6 +51,7 @@ _SIGS = {
     "hhsr_normalize_raw_u16": [P, I, I, I, I, U8P, DP, D, DP, P, P],
     "hhsr_normalize_raw_packed": [P, I, I, I, L, L, I, U8P, DP, D, DP, P, P],
     "hhsr_packed_row_bytes": [I, I, I64P],
+    "hhsr_linearize_raw_u16": [P, I, I, I, I, U8P, DP, D, DP, P, I, P, P, P, I, P, L, P, P],
     "hhsr_sharpness_workspace": [I, I, I, SZP],
     "hhsr_frame_sharpness": [PP, I, I, I, L, I, U8P, P, SZ, P, P],
     "hhsr_noise_profile_hist": [PP, I, I, I, L, U8P, FP, P, P],
@@ -132,6 +133,15 @@ PNG_SPEC_BYTES = 768  # HHSR_PNG_SPEC_BYTES: the code lengths and block header o
 LJPEG_OK, LJPEG_TRUNCATED, LJPEG_BAD_CODE, LJPEG_BAD_SEGMENT = 0, 1, 2, 3  # HHSR_LJPEG_*: a segment's status
 LJPEG_STATUS = ("OK", "TRUNCATED", "BAD_CODE", "BAD_SEGMENT")
 LJPEG_BAD_SAMPLE = 4  # HHSR_LJPEG_BAD_SAMPLE: hhsr_ljpeg_histogram's status for a sample at or above 2^P
+MAX_GAIN_MAPS = 4  # HHSR_MAX_GAIN_MAPS: gain maps per hhsr_linearize_raw_u16 call
+MAX_GAIN_POINTS = 64  # points of a gain map along one axis
+
+
+class GainMapDesc(C.Structure):
+    """hhsr_gain_map: one map of hhsr_linearize_raw_u16, its values at `offset` of the call's gains array."""
+    _fields_ = [("top", C.c_int32), ("left", C.c_int32), ("row_pitch", C.c_int32), ("col_pitch", C.c_int32),
+                ("points_v", C.c_int32), ("points_h", C.c_int32), ("spacing_v", C.c_double), ("spacing_h", C.c_double),
+                ("origin_v", C.c_double), ("origin_h", C.c_double), ("offset", C.c_int64)]
 
 
 class LjpegInfo(C.Structure):

@@ -3,7 +3,10 @@ GPU in the form the file holds them (read_dng_burst) — lossless-JPEG tiles and
 hhsr_ljpeg_decode, uncompressed 16-bit counts, or packed 10/12/14-bit rows — and normalised there.  Opt-in:
 ``config.dng = {"reader": "native"}`` (super_resolution.load_burst).  Every offset and count of a file is checked against
 its size before it is used; what the reader does not handle is a ValueError that names the tag.  PARITY.md, "DNG input",
-lists what this was never compared with: no file of a camera or of Adobe's converter, no rawpy / LibRaw decode."""
+lists what this was never compared with: no file of a camera or of Adobe's converter, no rawpy / LibRaw decode.
+``config.dng.linearization: apply`` (parse_dng / read_dng_burst with linearization=True) reads LinearizationTable,
+BlackLevelDeltaH / V and the GainMap opcodes of OpcodeList2 instead of refusing or ignoring them, and
+utils_dng.linearize_burst applies them on the GPU (PARITY.md, "DNG linearization")."""
 import ctypes
 import glob
 import os
@@ -14,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .utils_dng import normalize_burst, normalize_packed, packed_row_bytes
+from .utils_dng import linearize_burst, normalize_burst, normalize_packed, packed_row_bytes, unpack_raw
 
 MAX_IFD_ENTRIES = 512
 _TYPE_SIZE = {1: 1, 2: 1, 3: 2, 4: 4, 5: 8, 6: 1, 7: 1, 8: 2, 9: 4, 10: 8, 11: 4, 12: 8, 13: 4}
@@ -25,18 +28,28 @@ TAGS = {254: "NewSubFileType", 256: "ImageWidth", 257: "ImageLength", 258: "Bits
         324: "TileOffsets", 325: "TileByteCounts", 330: "SubIFDs", 33421: "CFARepeatPatternDim", 33422: "CFAPattern",
         34665: "ExifIFD", 34855: "ISOSpeedRatings", 50712: "LinearizationTable", 50713: "BlackLevelRepeatDim",
         50714: "BlackLevel", 50715: "BlackLevelDeltaH", 50716: "BlackLevelDeltaV", 50717: "WhiteLevel",
-        50721: "ColorMatrix1", 50728: "AsShotNeutral", 50729: "AsShotWhiteXY", 50761: "NoiseProfile"}
+        50721: "ColorMatrix1", 50728: "AsShotNeutral", 50729: "AsShotWhiteXY", 50761: "NoiseProfile", 50829: "ActiveArea",
+        51009: "OpcodeList2"}
 _ID = {name: tag for tag, name in TAGS.items()}
 
 # One stream of the raw image: where its bytes are in the file and the rectangle it covers
 Segment = namedtuple("Segment", "offset length x0 y0 seg_w seg_h")
 
 DngInfo = namedtuple("DngInfo", "path byte_order width height bits compression layout segments cfa_pattern black_levels "
-                                "white_level white_balance orientation xyz2cam noise_profile iso raw_ifd_offset file_size")
+                                "white_level white_balance orientation xyz2cam noise_profile iso raw_ifd_offset file_size "
+                                "linearization_table black_delta_h black_delta_v gain_maps", defaults=(None,) * 4)
 DngInfo.__doc__ = """What parse_dng reads from one file.  `layout`: "strips" or "tiles"; `segments`: Segment per strip / tile
 in file order; `cfa_pattern`: 2 x 2 list of 0 / 1 / 2; `black_levels`: (R, G, B); `white_balance`: 1 / AsShotNeutral (list of
 3) or None; `orientation`, `xyz2cam` (3 x 3 float32), `noise_profile` (list of floats) and `iso` (clamped to 100..3200): None
-when the tag is absent."""
+when the tag is absent.  Only with parse_dng(linearization=True), None otherwise and when the file has none:
+`linearization_table` (uint16 ndarray, 1 .. 65536 entries), `black_delta_h` / `black_delta_v` (float32 ndarrays of `width` /
+`height` entries; an all-zero tag is None), `gain_maps` (list of GainMap from OpcodeList2)."""
+
+GainMap = namedtuple("GainMap", "top left bottom right plane planes row_pitch col_pitch points_v points_h spacing_v spacing_h "
+                                "origin_v origin_h map_planes gains")
+GainMap.__doc__ = """One GainMap opcode (ID 9) of OpcodeList2 with the parameter names of the DNG specification; `gains`:
+float32 ndarray [points_v, points_h]."""
+MAX_GAIN_POINTS = 64  # per axis of a map: what hhsr_linearize_raw_u16 holds of one map row
 
 
 def _name(tag):
@@ -147,14 +160,132 @@ def _segments(t, ifd, W, H):
     return ("tiles" if tiled else "strips"), segs
 
 
-def parse_dng(path):
+def _opcode_list2(t, ifd, W, H):
+    """The GainMap records of OpcodeList2 (51009), or None without the tag or without a GainMap in it.  The list is
+    big-endian whatever the file's byte order: a LONG count, then per opcode OpcodeID, DNG version, flags and the byte size
+    of its parameters (LONG each) and the parameters.  Every size is checked against the tag's byte count before it is used.
+    Another opcode is skipped when its flag bit 0 (optional) is set and refused by its ID otherwise."""
+    tag = _ID["OpcodeList2"]
+    if tag not in ifd:
+        return None
+    typ, nbytes, at = ifd[tag]
+    name, path = _name(tag), t.path
+    if typ not in (1, 7):
+        raise ValueError(f"{path}: {name} has field type {typ}, BYTE or UNDEFINED expected")
+    end = at + nbytes
+
+    def need(p, n, what):
+        if p + n > end:
+            raise ValueError(f"{path}: {name} is truncated: {what} needs {n} bytes at byte {p - at} of {nbytes}")
+
+    need(at, 4, "the opcode count")
+    count = struct.unpack_from(">I", t.d, at)[0]
+    p, maps, phases = at + 4, [], set()
+    for i in range(count):
+        need(p, 16, f"the header of opcode {i}")
+        oid, _, flags, size = struct.unpack_from(">4I", t.d, p)
+        p += 16
+        need(p, size, f"the parameters of opcode {i} (OpcodeID {oid})")
+        if oid != 9:
+            if not flags & 1:
+                raise ValueError(f"{path}: {name}: opcode {i} with OpcodeID {oid} is not applied and not marked optional")
+            p += size
+            continue
+        what = f"{path}: {name}: opcode {i} (GainMap)"
+        if size < 76:
+            raise ValueError(f"{what}: parameter size {size} is below the 76 bytes of its fixed fields")
+        top, left, bottom, right, plane, planes, rp, cp, pv, ph = struct.unpack_from(">10I", t.d, p)
+        sv, sh, ov, oh = struct.unpack_from(">4d", t.d, p + 40)
+        mp = struct.unpack_from(">I", t.d, p + 72)[0]
+        for field, v in (("MapPointsV", pv), ("MapPointsH", ph)):
+            if not 1 <= v <= MAX_GAIN_POINTS:
+                raise ValueError(f"{what}: {field} {v} outside 1 .. {MAX_GAIN_POINTS}")
+        if mp != 1:
+            raise ValueError(f"{what}: MapPlanes {mp}: one plane per map only")
+        if planes != 1 or plane != 0:
+            raise ValueError(f"{what}: Plane {plane} / Planes {planes}: plane 0 of a one-plane image only")
+        if size != 76 + 4 * pv * ph * mp:
+            raise ValueError(f"{what}: parameter size {size} disagrees with MapPointsV x MapPointsH x MapPlanes = "
+                             f"{pv} x {ph} x {mp} gains ({76 + 4 * pv * ph * mp} bytes)")
+        for field, s, n in (("MapSpacingV", sv, pv), ("MapSpacingH", sh, ph)):
+            if n > 1 and not (np.isfinite(s) and s > 0):
+                raise ValueError(f"{what}: {field} {s} with {n} points: a positive spacing expected")
+        for field, o in (("MapOriginV", ov), ("MapOriginH", oh)):
+            if not np.isfinite(o):
+                raise ValueError(f"{what}: {field} {o} is not finite")
+        gains = np.frombuffer(t.d, ">f4", pv * ph, p + 76).astype(np.float32).reshape(pv, ph)
+        if not np.isfinite(gains).all():
+            raise ValueError(f"{what}: a non-finite gain")
+        if (rp, cp) == (1, 1):
+            if (top, left) != (0, 0):
+                raise ValueError(f"{what}: Top {top} / Left {left} with RowPitch = ColPitch = 1: 0 / 0 expected")
+            cover = {0, 1, 2, 3}
+        elif (rp, cp) == (2, 2):
+            if top > 1 or left > 1:
+                raise ValueError(f"{what}: Top {top} / Left {left} with RowPitch = ColPitch = 2: 0 or 1 expected")
+            cover = {top * 2 + left}
+        else:
+            raise ValueError(f"{what}: RowPitch {rp} / ColPitch {cp}: 1 / 1 (every pixel) or 2 / 2 (one Bayer plane) only")
+        if cover & phases:
+            raise ValueError(f"{what}: a second map for the pixels at Top {top} / Left {left}, RowPitch {rp} / ColPitch {cp}")
+        phases |= cover
+        if bottom < H or right < W:
+            raise ValueError(f"{what}: Bottom {bottom} / Right {right} do not reach the image's {H} x {W}: a map that "
+                             "covers part of the image is not applied")
+        maps.append(GainMap(top, left, bottom, right, plane, planes, rp, cp, pv, ph, sv, sh, ov, oh, mp, gains))
+        p += size
+    return maps or None
+
+
+def _linearization(t, raw, W, H):
+    """(linearization_table, black_delta_h, black_delta_v, gain_maps) of the raw IFD, each None when absent."""
+    path = t.path
+    tag = _ID["LinearizationTable"]
+    table = None
+    if tag in raw:
+        typ, count, _ = raw[tag]
+        if typ != 3:
+            raise ValueError(f"{path}: {_name(tag)} has field type {typ}, SHORT expected")
+        if not 1 <= count <= 65536:
+            raise ValueError(f"{path}: {_name(tag)} has {count} entries, 1 .. 65536 expected")
+        table = np.array(t.values(raw, tag), np.uint16)
+    deltas = []
+    for tag, n, axis in ((_ID["BlackLevelDeltaH"], W, "ImageWidth"), (_ID["BlackLevelDeltaV"], H, "ImageLength")):
+        d = None
+        if tag in raw:
+            if raw[tag][1] != n:
+                raise ValueError(f"{path}: {_name(tag)} has {raw[tag][1]} entries, {axis} = {n} expected")
+            d = np.array(t.values(raw, tag), np.float32)
+            if not np.isfinite(d).all():
+                raise ValueError(f"{path}: {_name(tag)} holds a non-finite entry")
+            d = d if d.any() else None
+        deltas.append(d)
+    maps = _opcode_list2(t, raw, W, H)
+    tag = _ID["ActiveArea"]
+    if tag in raw and (deltas[0] is not None or deltas[1] is not None or maps):
+        area = t.ints(raw, tag, 4)
+        if area != [0, 0, H, W]:
+            raise ValueError(f"{path}: {_name(tag)} {area} is not the whole image [0, 0, {H}, {W}]: the black deltas and the "
+                             "gain maps' relative coordinates are defined on the active area, and the full image is read")
+    return table, deltas[0], deltas[1], maps
+
+
+def parse_dng(path, linearization=False):
     """The DngInfo of one .dng file: classic TIFF (II / MM), the raw image in IFD0 or one of its SubIFDs (tag 330, one level):
     the IFD with NewSubFileType 0 and PhotometricInterpretation 32803 (CFA).  Refused by name (ValueError): BigTIFF, LinearRaw
     (34892), Compression other than 1 and 7, SamplesPerPixel != 1, FillOrder != 1, PlanarConfiguration != 1, a CFA that is not
     2 x 2 of R / G / B, BlackLevelRepeatDim other than 1 x 1 and 2 x 2, non-zero BlackLevelDeltaH / V, LinearizationTable,
     AsShotWhiteXY without AsShotNeutral.  ActiveArea, DefaultCrop and the opcode lists are ignored, as the reference ignores
     them (it reads rawpy's full raw_image).  A malformed container — an offset or count outside the file, an IFD loop, a
-    strip or tile table shorter than the image needs — is a ValueError naming the tag or offset."""
+    strip or tile table shorter than the image needs — is a ValueError naming the tag or offset.
+
+    `linearization=True` reads what is refused or ignored above instead, into the last four fields of the record:
+    LinearizationTable (SHORT, 1 .. 65536 entries), BlackLevelDeltaH / V (exactly ImageWidth / ImageLength entries) and the
+    GainMap opcodes of OpcodeList2 (_opcode_list2) — one map with RowPitch = ColPitch = 1 at Top = Left = 0, or up to four
+    with pitches 2 and Top, Left in {0, 1}, one per position of the 2 x 2 cell at most, each reaching the image's last row
+    and column, one plane, 1 .. 64 points per axis.  Anything else about them is a ValueError naming the tag, opcode or
+    field; so is an ActiveArea (50829) other than the whole image next to a non-zero delta or a map.  OpcodeList1 and
+    OpcodeList3 stay ignored.  utils_dng.linearize_burst applies the four."""
     path = os.fspath(path)
     with open(path, "rb") as f:
         data = f.read()
@@ -234,12 +365,16 @@ def parse_dng(path):
     else:  # by CFA position; green is the green cell on the red row (LibRaw's colour 1)
         r = cfa.index(0)
         black = (float(bl[r]), float(bl[r ^ 1]), float(bl[cfa.index(2)]))
-    for tag in (_ID["BlackLevelDeltaH"], _ID["BlackLevelDeltaV"]):
-        if any(v != 0 for v in (t.values(raw, tag, 65535) or [])):
-            raise ValueError(f"{path}: {_name(tag)} with a non-zero entry is not applied")
-    if _ID["LinearizationTable"] in raw:
-        raise ValueError(f"{path}: LinearizationTable (50712) is not applied")
-    wl = t.values(raw, _ID["WhiteLevel"], 4)
+    lin = (None,) * 4
+    if linearization:
+        lin = _linearization(t, raw, W, H)
+    else:
+        for tag in (_ID["BlackLevelDeltaH"], _ID["BlackLevelDeltaV"]):
+            if any(v != 0 for v in (t.values(raw, tag, 65535) or [])):
+                raise ValueError(f"{path}: {_name(tag)} with a non-zero entry is not applied")
+        if _ID["LinearizationTable"] in raw:
+            raise ValueError(f"{path}: LinearizationTable (50712) is not applied")
+    wl =t.values(raw, _ID["WhiteLevel"], 4)
     white = float(wl[0]) if wl else float((1 << bits) - 1)
 
     def either(tag, max_count):
@@ -272,7 +407,7 @@ def parse_dng(path):
         iso = t.ints(ifd0, _ID["ISOSpeedRatings"], 3)
     iso = min(3200, max(100, int(iso[0]))) if iso else None
     return DngInfo(path, t.byte_order, W, H, bits, comp, layout, segs, [cfa[:2], cfa[2:]], black, white, wb,
-                   int(ori[0]) if ori else None, xyz2cam, npf, iso, raw_off, t.n)
+                   int(ori[0]) if ori else None, xyz2cam, npf, iso, raw_off, t.n, *lin)
 
 
 # ---- lossless JPEG -------------------------------------------------------------------------------------------------------
@@ -407,7 +542,19 @@ def _uncompressed(data, info):
     return out
 
 
-def read_dng_burst(folder, device=None, decoder="host", mode="bayer"):
+def _same_linearization(a, b):
+    """The name of the first linearization field in which the records a and b differ, or None."""
+    for field in ("linearization_table", "black_delta_h", "black_delta_v"):
+        u, v = getattr(a, field), getattr(b, field)
+        if (u is None) != (v is None) or (u is not None and not np.array_equal(u, v)):
+            return field
+    u, v = a.gain_maps or [], b.gain_maps or []
+    if len(u) != len(v) or any(m[:-1] != n[:-1] or not np.array_equal(m.gains, n.gains) for m, n in zip(u, v)):
+        return "gain_maps"
+    return None
+
+
+def read_dng_burst(folder, device=None, decoder="host", mode="bayer", linearization=False):
     """Folder of .dng files -> the burst mapping process() takes: ``ref`` / ``comp`` as normalised float32 device tensors
     (what utils_dng.load_dng_burst returns), ``cfa_pattern``, ``white_balance``, ``iso``, ``orientation`` and ``xyz2cam`` when
     present, ``alpha`` / ``beta`` from NoiseProfile (the mean over the three planes; the first pair with `mode` "grey") and
@@ -415,13 +562,18 @@ def read_dng_burst(folder, device=None, decoder="host", mode="bayer"):
     metadata from file 0, as upstream.  Compression 7: every stream's entropy-coded bytes in one blob, decoded by the
     host function on up to 16 threads and uploaded as counts (`decoder` "host", the default: README, "Front end", has the
     measurement that decided it) or uploaded once and decoded by one launch (`decoder` "gpu", which the same measurement
-    favours from about 20 frames of 12 MP on); a stream whose status is not 0 is a ValueError naming file and segment.  ``debug``: {"infos": the DngInfo records, "plan": the LjpegPlan or None}."""
+    favours from about 20 frames of 12 MP on); a stream whose status is not 0 is a ValueError naming file and segment.  ``debug``: {"infos": the DngInfo records, "plan": the LjpegPlan or None}.
+    `linearization=True` (``config.dng.linearization: apply``): the files are parsed with parse_dng(linearization=True); the
+    table, deltas and maps of every file must equal those of file 0 (ValueError naming the file and the field); when file 0
+    has any of them, the whole burst goes through utils_dng.linearize_burst in place of normalize_burst — packed 10/12/14-bit
+    strips unpacked on the host first — and when it has none, through exactly the calls made without the keyword.
+    ``alpha`` / ``beta`` are passed on unchanged: NoiseProfile describes the values before the gain map."""
     if decoder not in ("gpu", "host"):
         raise ValueError(f"decoder {decoder!r}: 'gpu' or 'host'")
     paths = sorted(glob.glob(os.path.join(os.fspath(folder), "*.dng")))
     if not paths:
         raise FileNotFoundError("At least one raw .dng file must be present in the burst folder.")
-    infos = [parse_dng(p) for p in paths]
+    infos = [parse_dng(p, linearization=True) if linearization else parse_dng(p) for p in paths]
     i0 = infos[0]
     for info in infos[1:]:
         for field in ("width", "height", "bits", "compression", "cfa_pattern"):
@@ -429,6 +581,10 @@ def read_dng_burst(folder, device=None, decoder="host", mode="bayer"):
                 raise ValueError(f"{info.path}: {field} {getattr(info, field)} differs from {getattr(i0, field)} of {i0.path}")
         if info.compression == 1 and info.bits != 16 and info.layout != "strips":
             raise ValueError(f"{info.path}: packed tiles are not read")
+        field = _same_linearization(info, i0)
+        if field:
+            raise ValueError(f"{info.path}: {field} differs from that of {i0.path}: one table, one pair of deltas and one set "
+                             "of maps per burst")
     if i0.white_balance is None:
         raise ValueError(f"{i0.path}: AsShotNeutral (50728) is missing: no white balance")
     if i0.iso is None:
@@ -440,6 +596,13 @@ def read_dng_burst(folder, device=None, decoder="host", mode="bayer"):
     dev = device or torch.device("cuda", torch.cuda.current_device())
     levels = (i0.black_levels, i0.white_level, i0.white_balance, i0.cfa_pattern)
     plan = None
+    lin = None  # what linearize_burst takes beyond the levels, when file 0 brings any of it
+    if i0.linearization_table is not None or i0.black_delta_h is not None or i0.black_delta_v is not None or i0.gain_maps:
+        lin = dict(table=i0.linearization_table, delta_h=i0.black_delta_h, delta_v=i0.black_delta_v, gain_maps=i0.gain_maps)
+
+    def normalise(counts):  # (one call for the whole burst: table, deltas and maps are uploaded once)
+        return linearize_burst(counts, *levels, **lin, device=dev) if lin else normalize_burst(counts, *levels, device=dev)
+
     if i0.compression == 7:
         plan = plan_ljpeg(files, infos)
         counts, status = decode_ljpeg(plan, len(infos), i0.height, i0.width, dev, decoder)
@@ -448,12 +611,17 @@ def read_dng_burst(folder, device=None, decoder="host", mode="bayer"):
             path, seg = plan.names[int(bad[0])]
             raise ValueError(f"{path}: segment {seg}: lossless JPEG status {_lib.LJPEG_STATUS[int(status[bad[0]])]} "
                              f"({bad.size} of {status.size} segments failed)")
-        stack = normalize_burst(counts, *levels, device=dev)
+        stack = normalise(counts)
     elif i0.bits == 16:
-        stack = normalize_burst(np.stack([_uncompressed(d, i) for d, i in zip(files, infos)]), *levels, device=dev)
+        stack = normalise(np.stack([_uncompressed(d, i) for d, i in zip(files, infos)]))
     else:
         rows = np.stack([_uncompressed(d, i) for d, i in zip(files, infos)])
-        stack = normalize_packed(rows, i0.width, f"be{i0.bits}", *levels, device=dev)
+        if lin:
+            # hhsr_linearize_raw_u16 takes uint16 counts only: packed strips that need it are unpacked on the HOST
+            # (utils_dng.unpack_raw, NumPy).  Reading the packed layouts inside that kernel is a follow-up.
+            stack = normalise(unpack_raw(rows, i0.width, f"be{i0.bits}"))
+        else:
+            stack = normalize_packed(rows, i0.width, f"be{i0.bits}", *levels, device=dev)
     burst = {"ref": stack[0], "comp": stack[1:], "cfa_pattern": i0.cfa_pattern, "white_balance": i0.white_balance,
              "iso": i0.iso, "debug": {"infos": infos, "plan": plan}}
     if i0.orientation is not None:

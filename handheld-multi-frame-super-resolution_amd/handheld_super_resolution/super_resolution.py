@@ -822,21 +822,39 @@ def dng_options(config):
     return reader
 
 
+DNG_LINEARIZATION = ("refuse", "apply")
+
+
+def dng_linearization(config):
+    """What the native reader does with a file's LinearizationTable, BlackLevelDeltaH / V and GainMap opcodes:
+    config.dng.linearization = "refuse" (absent: the table and non-zero deltas are a ValueError, the maps are ignored) or
+    "apply" (dng.read_dng_burst(linearization=True): read and applied on the GPU).  ValueError for anything else, and for
+    "apply" with the rawpy reader, which has no such step."""
+    choice = str((config.get("dng", None) or {}).get("linearization", "refuse"))
+    if choice not in DNG_LINEARIZATION:
+        raise ValueError(f"config.dng.linearization {choice!r}: refuse or apply")
+    if choice == "apply" and dng_options(config) != "native":
+        raise ValueError("config.dng.linearization 'apply' needs config.dng.reader 'native': the rawpy reader applies none of it")
+    return choice
+
+
 def load_burst(burst_path, config):
     """The burst mapping of process(): `burst_path` itself, the arrays of an .npz file, or a folder of .dng files, which
     needs rawpy + exifread like the reference (absent from this image: ImportError) and takes the noise profile, ISO,
     orientation and colour matrix from the tags of file 0 — or, with ``config.dng.reader: native`` (dng_options, checked
     before the burst is touched), is read by dng.read_dng_burst with the standard library and the GPU alone; a file without
-    NoiseProfile then needs ``noise_model.source: estimate``.  ``mode: grey``: ``cfa_pattern`` / ``white_balance`` are
-    filled in."""
+    NoiseProfile then needs ``noise_model.source: estimate``.  ``config.dng.linearization: apply`` (dng_linearization,
+    checked there too) has that reader apply the files' linearization table, black deltas and gain maps.  ``mode: grey``:
+    ``cfa_pattern`` / ``white_balance`` are filled in."""
     reader = dng_options(config)
+    linearization = dng_linearization(config) == "apply"
     burst = burst_path
     if isinstance(burst_path, (str, os.PathLike)) and str(burst_path).endswith(".npz"):
         burst = dict(np.load(burst_path))
     elif isinstance(burst_path, (str, os.PathLike)) and reader == "native":
         from .dng import read_dng_burst
 
-        burst = read_dng_burst(burst_path, mode=config.mode)
+        burst = read_dng_burst(burst_path, mode=config.mode, linearization=linearization)
         if "alpha" not in burst and noise_options(config)[0] != "estimate" and config.noise_model.get("alpha", None) is None:
             raise ValueError(f"{burst['debug']['infos'][0].path}: NoiseProfile (50761) is missing: set "
                              "noise_model.source: estimate to measure the noise profile from the frames")

@@ -49,6 +49,106 @@ def normalize_burst(raw, black_levels, white_level, white_balance, cfa_pattern, 
     return out[0] if squeeze else out
 
 
+def _map_field(m, name):
+    return m[name] if isinstance(m, dict) else getattr(m, name)
+
+
+def _map_axis(n, origin, spacing, points):
+    """(i0, i1 as intp, fraction as float32) of the pixel centres of an axis of n pixels in a map of `points` points:
+    include/hhsr.h, "DNG linearization", step 3."""
+    i0, f = np.zeros(n, np.intp), np.zeros(n, np.float32)
+    i1 = i0.copy()
+    if points > 1:
+        u = ((np.arange(n, dtype=np.float64) + 0.5) / np.float64(n) - np.float64(origin)) / np.float64(spacing)
+        hi, mid = u >= points - 1, (u > 0) & (u < points - 1)
+        fl = np.floor(u[mid])
+        i0[hi] = i1[hi] = points - 1
+        i0[mid], i1[mid], f[mid] = fl.astype(np.intp), fl.astype(np.intp) + 1, (u[mid] - fl).astype(np.float32)
+    return i0, i1, f
+
+
+def gain_map_plane(gain_map, H, W):
+    """The gain of every pixel of an H x W image under one map (a dng.GainMap, or a mapping with its fields), float32
+    [H, W] on the host in NumPy: the map interpolated at the pixel centres as hhsr_linearize_raw_u16 does it, operation
+    by operation.  The map's Top / Left / pitches are not looked at: pixels it does not cover get the value they would have."""
+    m = np.asarray(_map_field(gain_map, "gains"), np.float32)
+    if m.ndim != 2:
+        raise ValueError("gain_map_plane: gains must be [MapPointsV, MapPointsH]")
+    r0, r1, fv = _map_axis(int(H), _map_field(gain_map, "origin_v"), _map_field(gain_map, "spacing_v"), m.shape[0])
+    c0, c1, fh = _map_axis(int(W), _map_field(gain_map, "origin_h"), _map_field(gain_map, "spacing_h"), m.shape[1])
+    one = np.float32(1)
+    tv = m[r0] * (one - fv)[:, None] + m[r1] * fv[:, None]  # [H, PH]: the vertical blend of every map column
+    return tv[:, c0] * (one - fh)[None, :] + tv[:, c1] * fh[None, :]
+
+
+def linearize_burst(raw, black_levels, white_level, white_balance, cfa_pattern, table=None, delta_h=None, delta_v=None,
+                    gain_maps=None, device=None):
+    """normalize_burst() with a DNG's LinearizationTable (`table`: up to 65536 uint16 entries), BlackLevelDeltaH / V
+    (`delta_h` [W], `delta_v` [H], float32) and GainMap opcodes (`gain_maps`: up to four dng.GainMap records or mappings
+    with their fields — one with pitches 1, or one per 2 x 2 position with pitches 2) applied on the GPU
+    (hhsr_linearize_raw_u16; include/hhsr.h states every operation).  The same input forms as normalize_burst; table,
+    deltas and gains may be device tensors already (read_dng_burst uploads them once).  With all four absent the result
+    equals normalize_burst's for integer levels.  NoiseProfile describes the values BEFORE the gain map: a map scales the
+    noise with the position, which nothing downstream models."""
+    dev = device or torch.device("cuda", torch.cuda.current_device())
+    arr = raw if isinstance(raw, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(raw))
+    if arr.dtype not in (torch.uint16, torch.int16):
+        if arr.dtype.is_floating_point:
+            raise TypeError("linearize_burst expects integer sensor counts (got %s): float data is taken as already "
+                            "normalised" % arr.dtype)
+        arr = to_uint16(arr)
+    squeeze = arr.dim() == 2
+    if squeeze:
+        arr = arr[None]
+    if arr.dim() != 3:
+        raise ValueError("raw must be [H, W] or [n, H, W]")
+    arr = arr.contiguous().to(dev, non_blocking=True)
+    n, H, W = arr.shape
+    bl = [float(v) for v in list(black_levels)[:3]]
+    wb = [float(v) for v in list(white_balance)[:3]]
+    if len(bl) < 3 or len(wb) < 3:
+        raise ValueError("black_levels and white_balance need one entry per colour (R, G, B)")
+
+    def vector(v, dtype, np_dtype, length, name):
+        if v is None:
+            return None
+        if not torch.is_tensor(v):
+            a = np.asarray(v)
+            if np_dtype == np.uint16 and (not np.issubdtype(a.dtype, np.integer) or (a.size and (a.min() < 0 or a.max() > 65535))):
+                raise ValueError(f"linearize_burst: {name} must hold integers in 0 .. 65535")
+            v = torch.as_tensor(np.ascontiguousarray(a.astype(np_dtype)))
+        if v.dim() != 1 or v.dtype not in ((torch.uint16, torch.int16) if np_dtype == np.uint16 else (dtype,)):
+            raise ValueError(f"linearize_burst: {name} must be a 1-D {np.dtype(np_dtype).name} array")
+        if not (v.numel() == length if length else 1 <= v.numel() <= 65536):
+            raise ValueError(f"linearize_burst: {name} has {v.numel()} entries" + (f", {length} expected" if length else ""))
+        return v.contiguous().to(dev, non_blocking=True)
+
+    tab = vector(table, torch.uint16, np.uint16, None, "table")
+    dh = vector(delta_h, torch.float32, np.float32, W, "delta_h")
+    dv = vector(delta_v, torch.float32, np.float32, H, "delta_v")
+    maps = list(gain_maps or [])
+    if len(maps) > _lib.MAX_GAIN_MAPS:
+        raise ValueError(f"linearize_burst: {len(maps)} gain maps, at most {_lib.MAX_GAIN_MAPS}")
+    descs, at, pieces = (_lib.GainMapDesc * max(1, len(maps)))(), 0, []
+    for i, m in enumerate(maps):
+        g = _map_field(m, "gains")
+        g = g if torch.is_tensor(g) else torch.as_tensor(np.ascontiguousarray(g, np.float32))
+        if g.dim() != 2 or g.dtype != torch.float32:
+            raise ValueError("linearize_burst: a map's gains must be float32 [MapPointsV, MapPointsH]")
+        descs[i] = _lib.GainMapDesc(*(int(_map_field(m, k)) for k in ("top", "left", "row_pitch", "col_pitch")), g.shape[0],
+                                    g.shape[1], *(float(_map_field(m, k)) for k in ("spacing_v", "spacing_h", "origin_v",
+                                                                                   "origin_h")), at)
+        at += g.numel()
+        pieces.append(g.reshape(-1).to(dev, non_blocking=True))
+    gains = torch.cat(pieces) if pieces else None
+    out = torch.empty((n, H, W), dtype=torch.float32, device=dev)
+    _lib.call("hhsr_linearize_raw_u16", _lib.ptr(arr), n, H, W, W, _lib.cfa_bytes(cfa_pattern), _lib.doubles(bl),
+              float(white_level), _lib.doubles(wb), _lib.ptr(tab), tab.numel() if tab is not None else 0, _lib.ptr(dh),
+              _lib.ptr(dv), ctypes.addressof(descs) if maps else None, len(maps), _lib.ptr(gains), at, _lib.ptr(out),
+              _lib.stream())
+    return out[0] if squeeze else out
+
+
 # Packed layouts of hhsr_normalize_raw_packed (include/hhsr.h states them operation by operation): name -> id
 PACKINGS = {"mipi10": 1, "mipi12": 2, "mipi14": 3, "be10": 4, "be12": 5, "be14": 6}
 

@@ -4,7 +4,9 @@
     python run_handheld.py --impath burst_folder --outpath out.dng output.format=dng [output.tile=128 output.predictor=1]
 
 --impath   a burst in an .npz file (the keys process() documents), or a folder of .dng files: where rawpy + exifread exist,
-           or with the override dng.reader=native read by this package itself (handheld_super_resolution/dng.py)
+           or with the override dng.reader=native read by this package itself (handheld_super_resolution/dng.py); with
+           dng.linearization=apply as well, the files' LinearizationTable, BlackLevelDeltaH / V and GainMap opcodes are
+           applied on the GPU instead of being refused or ignored
 --outpath  .png: 8-bit PNG;  .tif / .tiff: 16-bit uncompressed TIFF (post-processing as configured);  .dng with the override
            output.format=dng: a LinearRaw DNG of the merged linear image at 16 bits, post-processing switched off like
            upstream (whose DNG export runs exiftool and dng_validate on such a TIFF; here the file is coded on the GPU)

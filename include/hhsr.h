@@ -457,6 +457,55 @@ int hhsr_normalize_raw_packed(const uint8_t* raw, int n_frames, int H, int W, in
                               const double* white_balance, float* out, void* stream);
 int hhsr_packed_row_bytes(int W, int packing, int64_t* bytes_out);
 
+/* ---- DNG linearization: LinearizationTable, BlackLevelDeltaH / V and GainMap opcodes ----------------------------------
+ * hhsr_normalize_raw_u16 with the part of the DNG specification called "mapping raw values to linear reference values"
+ * applied on the way (dng.parse_dng(linearization=True) reads the tags; no counterpart in the reference, whose rawpy
+ * raw_image has none of it applied).  uint16 [n_frames][H][row_stride] -> float32 [n_frames][H][W], compact.  float32
+ * arithmetic, every operation rounded once, no contraction; the map coordinates in float64 (IEEE division in both).
+ * tests/dng_linearize_ref.py is the NumPy form, matched bit for bit.  For pixel (y, x): k = (y & 1) * 2 + (x & 1),
+ * c = cfa[k], and
+ *   1. lin = table ? table[min(count, table_len - 1)] : count, cast to float32.
+ *   2. b = (float32(black[c]) + delta_h[x]) + delta_v[y], a missing delta being 0.0f (added all the same);
+ *      den = float32(white) - b;  v = (lin - b) / den.
+ *   3. where position k has a map m with PV x PH points:
+ *        u = ((y + 0.5) / H - origin_v) / spacing_v  in float64; PV == 1 or u <= 0: r0 = r1 = 0, fv = 0;
+ *        u >= PV - 1: r0 = r1 = PV - 1, fv = 0; otherwise r0 = floor(u), r1 = r0 + 1, fv = float32(u - r0);
+ *        the same along x with W, origin_h, spacing_h, PH gives c0, c1, fh;
+ *        t0 = m[r0][c0] * (1 - fv) + m[r1][c0] * fv;  t1 the same at c1;  g = t0 * (1 - fh) + t1 * fh;  v = v * g.
+ *      A position without a map is not multiplied.
+ *   4. v = v * float32(wb[c] / wb[1]).
+ * No clipping, as in hhsr_normalize_raw_u16, whose bits this gives when table, deltas and maps are all absent and the
+ * levels are integers (there den is float32(white - black[c]), rounded from the float64 difference; here it is the float32
+ * difference of the rounded levels: equal whenever both levels are exact in float32).
+ * The coordinate rule is the DNG specification's "relative coordinates" over the whole image with the pixel centre at
+ * + 0.5, AS READ HERE: never compared with Adobe's DNG SDK, dng_validate, LibRaw or a camera's file.
+ * table: DEVICE uint16[table_len], 1 .. 65536 entries, or NULL with table_len 0.  delta_h: DEVICE float32[W], delta_v:
+ * DEVICE float32[H], either may be NULL.  maps: HOST, n_maps <= HHSR_MAX_GAIN_MAPS descriptors; gains: DEVICE
+ * float32[gains_len] holding every map row-major at its `offset`.  Either ONE map with row_pitch = col_pitch = 1 and
+ * top = left = 0, which covers every position, or maps with row_pitch = col_pitch = 2 and top, left in {0, 1}, at most one
+ * per position top * 2 + left.  A map's spacing along an axis with one point is not read.
+ * row_stride is the pitch of hhsr_normalize_raw_u16 (elements between rows of raw; frame n starts at
+ * raw + n * H * row_stride): with W and row_stride multiples of 8 a thread converts 8 counts with one 16-byte load,
+ * otherwise count by count, the same operations; tests/test_dng_linearize_gpu.py holds its padded and guarded cases.
+ * Error -1: a null raw / cfa / black_levels / white_balance / out; n_frames, H or W <= 0; n_frames or H > 65535;
+ * W > INT32_MAX - 2048; row_stride < W; raw or out not 16-byte aligned; white_balance[1] == 0; cfa[k] > 2; a table with
+ * table_len outside 1 .. 65536 or table_len != 0 without one; n_maps outside 0 .. 4, or maps / gains NULL with n_maps > 0;
+ * points outside 1 .. 64; an offset with which a map leaves gains[0 .. gains_len); a non-finite origin; a spacing that
+ * is not finite and > 0 on an axis with more than one point; pitches other than 1, 1 / 2, 2; top or left outside what
+ * the pitch allows; two maps for one position. */
+#define HHSR_MAX_GAIN_MAPS 4
+typedef struct hhsr_gain_map {
+    int32_t top, left, row_pitch, col_pitch;
+    int32_t points_v, points_h;
+    double spacing_v, spacing_h, origin_v, origin_h;
+    int64_t offset; /* of m[0][0] in gains, in floats */
+} hhsr_gain_map;
+int hhsr_linearize_raw_u16(const uint16_t* raw, int n_frames, int H, int W, int row_stride, const uint8_t cfa[4],
+                           const double* black_levels, double white_level, const double* white_balance,
+                           const uint16_t* table, int table_len, const float* delta_h, const float* delta_v,
+                           const hhsr_gain_map* maps, int n_maps, const float* gains, int64_t gains_len, float* out,
+                           void* stream);
+
 /* ---- reference selection: the sharpness score of a burst's candidate base frames ---------------------------------------
  * The reference takes file 0 of the burst as its base frame (utils_dng.py:77); the burst pipelines the algorithm comes from
  * (HDR+; Wronski et al.) take the sharpest of the first few frames, scored by the gradients of the raw green channel.  No
